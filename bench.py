@@ -9,7 +9,14 @@ steps).  Synthetic 1M-transition buffer resident in HBM (no Atari frames
 offline).  Multi-GPU (torchrun): one learner + one 1M buffer per GPU, flat
 gradient all-reduced over RCCL each step (weak scaling).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, primes and warms up, times the K steps and prints the result line.
+--dump-outputs DIR also writes what the learner holds after the last timed step (the arrays
+a caller of ``train_gradient_steps`` is left with) as DIR/<name>.npy; the inputs are seeded,
+so two builds run with the same arguments can be compared output for output.  --full adds
+the supplementary measurements to the line: the gather kernel's roofline, BASELINE configs
+2 and 5, the bf16 throughput row and the CPU baseline.
 """
 import argparse
 import ctypes
@@ -40,14 +47,22 @@ def parse(argv=None):
   ap.add_argument('--batch', type=int, default=32)
   ap.add_argument('--actions', type=int, default=9)
   ap.add_argument('--no-graph', action='store_true')
+  ap.add_argument('--full', action='store_true',
+                  help='after the headline, also measure what the line reports beside it: the '
+                       'gather kernel\'s roofline and, at N = 1, BASELINE configs 2 and 5, the '
+                       'bf16 throughput row and the CPU baseline (each has its --skip flag)')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help='after the timed steps, write what the learner holds after the last of '
+                       'them (final_outputs) as DIR/<name>.npy (rank 0)')
   ap.add_argument('--cpu-seconds', type=float, default=12.0)
-  ap.add_argument('--skip-cpu-baseline', action='store_true')
+  ap.add_argument('--skip-cpu-baseline', action='store_true', help='--full: no CPU baseline')
   ap.add_argument('--skip-configs', action='store_true',
-                  help='do not time BASELINE configs 2 and 5 after the headline (N = 1)')
+                  help='--full: do not time BASELINE configs 2 and 5 after the headline (N = 1)')
   ap.add_argument('--per-call', action='store_true',
                   help='drive the agent by update_period _train_step() calls per gradient '
                        'step (one graph replay per step) instead of train_gradient_steps')
-  ap.add_argument('--gather-iters', type=int, default=400)
+  ap.add_argument('--gather-iters', type=int, default=400,
+                  help='--full: launches in the gather roofline\'s timed graph')
   ap.add_argument('--schedules', default=None,
                   help='N > 1 (or --force-dist): comma-separated data-parallel schedules to time, '
                        'one after the other on fresh agents, the headline from the fastest -- '
@@ -62,7 +77,7 @@ def parse(argv=None):
                   help='N > 1 over RCCL: the learner\'s own communicators (parallel.RcclComm) '
                        'or torch.distributed\'s collectives')
   ap.add_argument('--skip-bf16', action='store_true',
-                  help='do not time the separate bf16 throughput row (N = 1)')
+                  help='--full: do not time the separate bf16 throughput row (N = 1)')
   ap.add_argument('--bf16-child', action='store_true', help=argparse.SUPPRESS)
   ap.add_argument('--force-dist', action='store_true',
                   help='one rank only: run the N > 1 learner schedule over a one-rank RCCL group '
@@ -197,6 +212,33 @@ def timed_steps(agent, steps, warmup, per_call=False, pg=None, deadline=None, pr
   finally:
     gc.enable()
   return elapsed, prime
+
+
+MAX_DUMP_BYTES = 64 << 20
+
+
+def final_outputs(agent):
+  """What a caller of ``train_gradient_steps`` is left with after its last step, as host
+  arrays (float32 as computed; the indices, integers, as float64): both networks' flat
+  parameters, and the last step's sampled indices and probabilities, per-sample loss and
+  the priorities it wrote back."""
+  t = agent._replay.transition
+  out = {'online_params': agent.online_convnet.fp.flat,
+         'target_params': agent.target_convnet.fp.flat,
+         'loss': agent._loss_out['loss'],
+         'priorities': agent._loss_out['priorities'],
+         'sampling_probabilities': t['sampling_probabilities'],
+         'indices': t['indices'].double()}
+  out = {k: v.detach().cpu().numpy() for k, v in out.items()}
+  assert all(v.dtype in (np.float32, np.float64) for v in out.values())
+  assert sum(v.nbytes for v in out.values()) <= MAX_DUMP_BYTES
+  return out
+
+
+def dump_outputs(directory, outputs):
+  os.makedirs(directory, exist_ok=True)
+  for name, a in outputs.items():
+    np.save(os.path.join(directory, name + '.npy'), a)
 
 
 def other_configs(device, steps):
@@ -534,6 +576,7 @@ def main(argv=None):
                'zero1': {'shard_optimizer': True}}
   assert all(n in kwargs_of for n in names), names
   schedules = {}
+  outputs = {}
   agent = None
   for name in names:
     if first_clean and any('_elapsed' in v for v in schedules.values()):
@@ -608,6 +651,8 @@ def main(argv=None):
     if err is not None:
       raise RuntimeError(err)
     assert np.isfinite(loss), 'non-finite loss'
+    if args.dump_outputs and rank == 0:
+      outputs[name] = final_outputs(agent)
     entry = {
         'value': round(world * args.steps / elapsed, 2), 'ms_per_step': round(1e3 * elapsed / args.steps, 4),
         'per_rank_ms_per_step': [round(1e3 * e / args.steps, 4) for e in per_rank],
@@ -636,26 +681,40 @@ def main(argv=None):
                           schedules[best]['final_mean_loss'])
   for v in schedules.values():
     v.pop('_elapsed', None)
+  if args.dump_outputs and rank == 0:
+    dump_outputs(args.dump_outputs, outputs[best])
+  del outputs
 
-  if agent is None:                 # the last schedule could not be built: time the gather on the best's
-    agent = build_agent(args.actions, args.capacity, args.batch, dev, pg=pg,
-                        use_hip_graph=not args.no_graph, native_comm=args.comm == 'native',
-                        **AGENT_OVERRIDES, **kwargs_of[best])
-    fill_synthetic(agent._replay.memory, args.actions, seed=1 + rank)
-  graph_us, algo_bytes, gname = time_gather(agent, args.gather_iters)
-  large = time_gather_large(agent)
-  traffic, traffic_src = gather_traffic(args.batch)
-  achieved = algo_bytes / (graph_us * 1e-6) / 1e9
+  # everything from here to the line is supplementary and runs under --full only
+  roofline = None
+  if args.full:
+    if agent is None:               # the last schedule could not be built: time the gather on the best's
+      agent = build_agent(args.actions, args.capacity, args.batch, dev, pg=pg,
+                          use_hip_graph=not args.no_graph, native_comm=args.comm == 'native',
+                          **AGENT_OVERRIDES, **kwargs_of[best])
+      fill_synthetic(agent._replay.memory, args.actions, seed=1 + rank)
+    graph_us, algo_bytes, gname = time_gather(agent, args.gather_iters)
+    large = time_gather_large(agent)
+    traffic, traffic_src = gather_traffic(args.batch)
+    achieved = algo_bytes / (graph_us * 1e-6) / 1e9
+    roofline = {'kernel': gname + ' (frame-stack gather + /255, state+next_state)',
+                'bound': 'hbm', 'achieved': round(achieved, 1), 'peak': HBM_PEAK_GBS,
+                'unit': 'GB/s', 'frac': round(achieved / HBM_PEAK_GBS, 4),
+                'traffic': traffic, 'traffic_source': traffic_src,
+                'algo_bytes_per_launch': algo_bytes,
+                'avg_launch_us': round(graph_us, 3),
+                'same_kernel_batch_1024': large}
 
   configs = None
-  if rank == 0 and world == 1 and not args.skip_configs and not args.force_dist:
+  if (args.full and rank == 0 and world == 1 and not args.skip_configs
+      and not args.force_dist):
     del agent
     gc.collect()
     torch.cuda.empty_cache()
     configs = other_configs(dev, args.steps)
 
   bf16 = None
-  if rank == 0 and world == 1 and not args.force_dist and not args.skip_bf16:
+  if args.full and rank == 0 and world == 1 and not args.force_dist and not args.skip_bf16:
     agent = None
     gc.collect()
     torch.cuda.empty_cache()
@@ -663,7 +722,7 @@ def main(argv=None):
     bf16 = bf16_throughput(args)
 
   cpu = None
-  if rank == 0 and world == 1 and not args.skip_cpu_baseline:
+  if args.full and rank == 0 and world == 1 and not args.skip_cpu_baseline:
     cpu = cpu_baseline(args.cpu_seconds, args.actions, args.batch)
 
   if rank == 0:
@@ -685,16 +744,12 @@ def main(argv=None):
                                      'allreduce': ', all-reduce over RCCL',
                                      'peer': ', peer-memory exchange on one stream'}.get(best, ''),
                    'hip_graph': not args.no_graph},
-        'roofline': {'kernel': gname + ' (frame-stack gather + /255, state+next_state)',
-                     'bound': 'hbm', 'achieved': round(achieved, 1), 'peak': HBM_PEAK_GBS,
-                     'unit': 'GB/s', 'frac': round(achieved / HBM_PEAK_GBS, 4),
-                     'traffic': traffic, 'traffic_source': traffic_src,
-                     'algo_bytes_per_launch': algo_bytes,
-                     'avg_launch_us': round(graph_us, 3),
-                     'same_kernel_batch_1024': large},
+        # the gather kernel against HBM peak, timed in launches of its own (--full; else null)
+        'roofline': roofline,
         # supplementary: the whole step against the fp32 matrix peak (the CNN's fp32 MFMA
         # work; the step is launch- and latency-bound at B = 32, not MFMA-bound)
         'step_mfma': step_mfma(args.actions, args.batch, elapsed / args.steps),
+        'full': args.full,
         'cpu_baseline': cpu,
         'final_mean_loss': round(loss, 8),
         'gc_disabled_in_timed_window': True,

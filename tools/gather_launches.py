@@ -1,5 +1,5 @@
 """The gather launches bench.py's ``roofline`` times, read back from a rocprofv3 kernel trace
-of the same command (``rocprofv3 --kernel-trace --stats -- python3 bench.py ...``).
+of the same command (``rocprofv3 --kernel-trace --stats -- python3 bench.py --full ...``).
 
 bench.time_gather launches k_gather_nhwc4 at the bench batch (grid 8 x B*2 blocks of 64) 10
 times eagerly, then replays a graph of ``iters`` launches twice (a warm replay and the timed
