@@ -292,11 +292,19 @@ struct EpiMaskPix {          // EpiMask on a sub-pixel class: row m -> its NHWC 
   float* out;
   const float* act;
   static constexpr bool kPrefetch = true;
-  __device__ __forceinline__ float pf(int m, int n) const {
-    return act[(int64_t)SP::pixel(m) * C + n];
+  // kPfOffset: the tile kernel works the element's offset out once (poff: the divisions of
+  // SP::pixel) and keeps that one register from the mask prefetch to the store, both through
+  // buffer descriptors (scalar base + 32-bit offset), instead of two 64-bit addresses
+  static constexpr bool kPfOffset = true;
+  __device__ __forceinline__ int poff(int m, int n) const { return SP::pixel(m) * C + n; }
+  __device__ __forceinline__ float pf_at(int off) const { return bload1(act, off, true); }
+  __device__ __forceinline__ void apply_at(int off, float v, float a) const {
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(a > 0.0f ? v : 0.0f), rsrc(out), off * 4,
+                                          0, 0);
   }
+  __device__ __forceinline__ float pf(int m, int n) const { return pf_at(poff(m, n)); }
   __device__ __forceinline__ void apply(int m, int n, float v, float a) const {
-    out[(int64_t)SP::pixel(m) * C + n] = a > 0.0f ? v : 0.0f;
+    apply_at(poff(m, n), v, a);
   }
   __device__ __forceinline__ void operator()(int m, int n, float v, int) const {
     apply(m, n, v, pf(m, n));
@@ -579,6 +587,15 @@ struct HasPf {
 template <class EP>
 struct HasPf<EP, decltype((void)EP::kPrefetch)> {
   static constexpr bool value = EP::kPrefetch;
+};
+
+template <class EP, class = void>
+struct HasPfOff {
+  static constexpr bool value = false;
+};
+template <class EP>
+struct HasPfOff<EP, decltype((void)EP::kPfOffset)> {
+  static constexpr bool value = EP::kPfOffset;
 };
 
 template <class EP, class = void>
@@ -900,10 +917,15 @@ using X6Of = typename std::conditional<kFast, X6Img<ROWS, BKT>, X6ImgT<ROWS, BKT
 // for launches with several rounds of blocks, two 16-wave blocks per CU); else
 // while they run (one more fetch in flight, for single-round launches).
 // kX6: the split-bf16 matrix-core form (block-shared staging only).
-template <int WM, int WN, int WK, class AL, class BL, class EP, bool kLate = true, bool kX6 = false>
-__device__ __forceinline__ void igemm_block(const AL& A, const BL& B, const EP& E, int M, int N,
-                                            int K, int kchunk, int bx, int by, int bz,
+// KS, NS > 0: K (one slice, no split: the K loop runs exactly once) and N known at compile
+// time -- the k / n bounds tests and the loop's next-slice addresses then cost no registers.
+template <int WM, int WN, int WK, class AL, class BL, class EP, bool kLate = true, bool kX6 = false,
+          int KS = 0, int NS = 0>
+__device__ __forceinline__ void igemm_block(const AL& A, const BL& B, const EP& E, int M, int N_,
+                                            int K_, int kchunk_, int bx, int by, int bz_,
                                             float* smem, int tid_base = 0) {
+  static_assert(KS == 0 || KS == Tile<WM, WN, WK>::BKT, "a static K is one whole slice");
+  const int N = NS ? NS : N_, K = KS ? KS : K_, kchunk = KS ? KS : kchunk_, bz = KS ? 0 : bz_;
   using TL = Tile<WM, WN, WK>;
   constexpr int T = TL::T, BM = TL::BM, BN = TL::BN, BKT = TL::BKT;
   constexpr int SA = BM + (AL::kFast ? 1 : 4), SB = BN + (BL::kFast ? 1 : 4);
@@ -964,7 +986,9 @@ __device__ __forceinline__ void igemm_block(const AL& A, const BL& B, const EP& 
   // reduction elements, loaded now (clamped, never branching); see kPrefetch
   constexpr int NE = (OUT + T - 1) / T;
   constexpr bool kPf = WK > 1 && HasPf<EP>::value && NE <= 2;
+  constexpr bool kPfOff = kPf && HasPfOff<EP>::value;
   float pfv[NE];
+  int pfo[NE];               // kPfOff: the (clamped) element's offset, kept for the store
   if constexpr (kPf) {
 #pragma unroll
     for (int i = 0; i < NE; ++i) {
@@ -972,7 +996,12 @@ __device__ __forceinline__ void igemm_block(const AL& A, const BL& B, const EP& 
       const int tile = e >> 10, r = (e >> 6) & 15, l = e & 63;
       const int m = m0 + (tile % WM) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (l >> 5);
       const int n = n0 + (tile / WM) * 32 + (l & 31);
-      pfv[i] = E.pf(min(m, M - 1), min(n, N - 1));
+      if constexpr (kPfOff) {
+        pfo[i] = E.poff(min(m, M - 1), min(n, N - 1));
+        pfv[i] = E.pf_at(pfo[i]);
+      } else {
+        pfv[i] = E.pf(min(m, M - 1), min(n, N - 1));
+      }
     }
   }
   f32x16 acc;
@@ -1219,7 +1248,11 @@ __device__ __forceinline__ void igemm_block(const AL& A, const BL& B, const EP& 
       const int tile = e >> 10, r = (e >> 6) & 15, l = e & 63;
       const int m = m0 + (tile % WM) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (l >> 5);
       const int n = n0 + (tile / WM) * 32 + (l & 31);
-      if (m < M && n < N) E.apply(m, n, v, pfv[i]);
+      if constexpr (kPfOff) {          // in range, the clamped offset is the element's own
+        if (m < M && n < N) E.apply_at(pfo[i], v, pfv[i]);
+      } else {
+        if (m < M && n < N) E.apply(m, n, v, pfv[i]);
+      }
     }
     return;
   }

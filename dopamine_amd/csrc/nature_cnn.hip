@@ -25,7 +25,7 @@
 // Activations are NHWC fp32; weights live in the flat parameter buffer as
 // conv (out, kh, kw, in) and FC (out, in) -- the GEMM's natural [M][K] layouts.
 #include <algorithm>
-
+#include <cassert>
 
 #include "cnn_tile.h"
 #include "c51_dev.h"
@@ -42,7 +42,8 @@ namespace cnn {
 // the same block size kGroupT, and the block's LDS is the largest op's.
 constexpr int kGroupT = 1024;
 
-template <int WM, int WN, int WK, class AL, class BL, class EP, bool kLate = true>
+template <int WM, int WN, int WK, class AL, class BL, class EP, bool kLate = true, int KS = 0,
+          int NS = 0>
 struct GemmOp {
   static constexpr int kT = 64 * WM * WN * WK;
   static constexpr bool kLateFetch = kLate;
@@ -53,8 +54,8 @@ struct GemmOp {
   int M, N, K, kchunk, gx, gy, gz;
   __device__ __forceinline__ void run(int blk, float* smem, int tid_base = 0) const {
     const int bx = blk % gx, by = (blk / gx) % gy, bz = blk / (gx * gy);
-    igemm_block<WM, WN, WK, AL, BL, EP, kLate, cnn_x6<WM, WN, WK, AL>()>(a, b, e, M, N, K, kchunk,
-                                                                      bx, by, bz, smem, tid_base);
+    igemm_block<WM, WN, WK, AL, BL, EP, kLate, cnn_x6<WM, WN, WK, AL>(), KS, NS>(
+        a, b, e, M, N, K, kchunk, bx, by, bz, smem, tid_base);
   }
   __host__ __device__ int blocks() const { return gx * gy * gz; }
 };
@@ -897,9 +898,13 @@ void k_grouped(GroupArgs<Ops...> g, Ops... ops) {
 
 // Launch context: a dry run only sizes the workspace, so the two can never disagree.
 // a grouped GEMM op; split-K ops write slabs into ws + off (EpiPartial)
-template <int WM, int WN, int WK, bool kLate = true, class AL, class BL, class EP>
-GemmOp<WM, WN, WK, AL, BL, EP, kLate> gemm_op(AL a, BL b, EP e, int M, int N, int K, int kchunk) {
-  GemmOp<WM, WN, WK, AL, BL, EP, kLate> op{a, b, e, M, N, K, kchunk, 0, 0, 0};
+template <int WM, int WN, int WK, bool kLate = true, int KS = 0, int NS = 0, class AL, class BL,
+          class EP>
+GemmOp<WM, WN, WK, AL, BL, EP, kLate, KS, NS> gemm_op(AL a, BL b, EP e, int M, int N, int K,
+                                                      int kchunk) {
+  // constants (igemm_block's KS / NS) must be the op's own sizes: the kernel reads no others
+  assert((KS == 0 || (K == KS && kchunk == KS)) && (NS == 0 || N == NS));
+  GemmOp<WM, WN, WK, AL, BL, EP, kLate, KS, NS> op{a, b, e, M, N, K, kchunk, 0, 0, 0};
   op.gx = (M + 32 * WM - 1) / (32 * WM);
   op.gy = (N + 32 * WN - 1) / (32 * WN);
   op.gz = (K + kchunk - 1) / kchunk;
@@ -965,14 +970,16 @@ struct FwdOps {
   static int fc1_chunk() { return split_chunk(kFlat, kSplitFc1, 32 * 16); }
   static int fc1_slabs() { return (kFlat + fc1_chunk() - 1) / fc1_chunk(); }
   static size_t ws_floats(int B) { return (size_t)fc1_slabs() * B * kHidden; }
+  // conv1, conv2 and fc2 are one K slice each (K = 32 x the tile's waves): K (and the convs'
+  // N) go to the tile as constants, as for the sub-pixel tiles (subpix_op)
   template <bool kLate = true>
   auto conv1() const {
-    return gemm_op<1, 1, 8, kLate>(Im2col<Conv1>{x}, RowK{p->conv1_w, Conv1::K},
+    return gemm_op<1, 1, 8, kLate, Conv1::K, 32>(Im2col<Conv1>{x}, RowK{p->conv1_w, Conv1::K},
                             EpiBiasAct{a->a1, p->conv1_b, 32, true}, B * 441, 32, Conv1::K, Conv1::K);
   }
   template <bool kLate = true>
   auto conv2() const {
-    return gemm_op<1, 1, 16, kLate>(Im2col<Conv2>{a->a1}, RowK{p->conv2_w, Conv2::K},
+    return gemm_op<1, 1, 16, kLate, Conv2::K, 64>(Im2col<Conv2>{a->a1}, RowK{p->conv2_w, Conv2::K},
                              EpiBiasAct{a->a2, p->conv2_b, 64, true}, B * 121, 64, Conv2::K, Conv2::K);
   }
   template <bool kLate = true>
@@ -990,7 +997,7 @@ struct FwdOps {
                                      EpiBiasAct{a->h, p->fc1_b, kHidden, true}};
   }
   auto fc2() const {
-    return gemm_op<1, 1, 16>(RowK{a->h, kHidden}, RowK{p->fc2_w, kHidden},
+    return gemm_op<1, 1, 16, true, kHidden>(RowK{a->h, kHidden}, RowK{p->fc2_w, kHidden},
                              EpiBiasAct{a->out, p->fc2_b, p->n_out, false}, B, p->n_out, kHidden,
                              kHidden);
   }
@@ -1155,7 +1162,9 @@ void forward_head(Ctx& c, const FwdOps& f) {
 template <int PY, int PX>
 auto subpix_op(const dq_cnn_params* p, const dq_cnn_acts* a, dq_cnn_acts* d, int B) {
   using SP = SubPix<Conv2, PY, PX>;
-  return gemm_op<1, 1, 8, true>(SubPixDy<Conv2, PY, PX>{d->a2}, SubPixW<Conv2, PY, PX>{p->conv2_w},
+  static_assert(SP::K == Tile<1, 1, 8>::BKT, "one K slice: the tile takes K and N as constants");
+  return gemm_op<1, 1, 8, true, SP::K, Conv2::CI>(
+                          SubPixDy<Conv2, PY, PX>{d->a2}, SubPixW<Conv2, PY, PX>{p->conv2_w},
                           EpiMaskPix<SP, Conv2::CI>{d->a1, a->a1}, B * SP::NY * SP::NX, Conv2::CI,
                           SP::K, SP::K);
 }
@@ -1318,7 +1327,7 @@ void backward_grouped(Ctx& c, const dq_cnn_params* p, const dq_cnn_params* g, in
   auto dW_fc2 = gemm_op<4, 4, 1>(ColKScalar{dout, NO}, ColKOnes{a->h, kHidden},
                                  EpiGrad{g->fc2_w, g->fc2_b, kHidden},
                                  NO, kHidden + 1, B, B);
-  auto dX_fc1 = gemm_op<1, 1, 16, kB1Late>(RowK{d->h, kHidden}, ColK{p->fc1_w, kFlat},
+  auto dX_fc1 = gemm_op<1, 1, 16, kB1Late, kHidden, kFlat>(RowK{d->h, kHidden}, ColK{p->fc1_w, kFlat},
                                   EpiMask{d->a3, a->a3, kFlat}, B, kFlat, kHidden, kHidden);
   auto dW_fc1 = gemm_op<4, 4, 1>(ColK{d->h, kHidden}, ColKOnes{a->a3, kFlat},
                                  EpiGrad{g->fc1_w, g->fc1_b, kFlat},
@@ -1493,7 +1502,7 @@ void backward_peer(Ctx& c, const dq_cnn_params* p, const dq_cnn_params* g, int B
   const size_t o1 = c.take((size_t)nz1 * 32 * (Conv1::K + 1));
   float* ws = c.ws;
   if (c.dry) return;
-  auto dX_fc1 = gemm_op<1, 1, 16, kB1Late>(RowK{d->h, kHidden}, ColK{p->fc1_w, kFlat},
+  auto dX_fc1 = gemm_op<1, 1, 16, kB1Late, kHidden, kFlat>(RowK{d->h, kHidden}, ColK{p->fc1_w, kFlat},
                                            EpiMask{d->a3, a->a3, kFlat}, B, kFlat, kHidden, kHidden);
   auto dW_fc1 = gemm_op<4, 4, 1>(ColK{d->h, kHidden}, ColKOnes{a->a3, kFlat},
                                  EpiGrad{g->fc1_w, g->fc1_b, kFlat}, kHidden, kFlat + 1, B, B);
