@@ -145,15 +145,22 @@ def _flat_nhwc(a):
   return a.permute(0, 2, 3, 1).reshape(a.shape[0], -1)
 
 
+# the convolutions' TF SAME paddings (left, right, top, bottom), strides and NHWC input /
+# output shapes: 84 -> 21 -> 11 -> 11 (conv2's pad is the asymmetric one, 1 before, 2 after)
+_CONVS = {'conv1': ((2, 2, 2, 2), 4, (84, 84, 4), (21, 21, 32)),
+          'conv2': ((1, 2, 1, 2), 2, (21, 21, 32), (11, 11, 64)),
+          'conv3': ((1, 1, 1, 1), 1, (11, 11, 64), (11, 11, 64))}
+
+
 def _graph(P, x_nhwc, masks, taus=None):
   """The layers of forward() / iqn_forward() as a DAG: (layers, their ReLU masks in their
   output layouts (None: no ReLU), the output layer)."""
   x = x_nhwc.permute(0, 3, 1, 2)
   mask = lambda name, nhwc, shape: _relu(torch.ones(shape, dtype=torch.float64), masks, name, nhwc)
   L = []
-  c1 = _Layer('conv1', _conv((2, 2, 2, 2), 4), [None], {0: x})
-  c2 = _Layer('conv2', _conv((1, 2, 1, 2), 2), [c1])
-  c3 = _Layer('conv3', _conv((1, 1, 1, 1), 1), [c2])
+  c1 = _Layer('conv1', _conv(*_CONVS['conv1'][:2]), [None], {0: x})
+  c2 = _Layer('conv2', _conv(*_CONVS['conv2'][:2]), [c1])
+  c3 = _Layer('conv3', _conv(*_CONVS['conv3'][:2]), [c2])
   L += [c1, c2, c3]
   if taus is None:
     f1 = _Layer('fc1', lambda xs, w, b: F.linear(_flat_nhwc(xs[0]), w, b), [c3])
@@ -273,3 +280,106 @@ def abs_grad(P, x_nhwc, masks, gout, gout_abs):
 def iqn_abs_grad(P, x_nhwc, taus, masks, gout, gout_abs):
   """abs_grad for iqn_forward (rows q B + b; masks a1, a2, a3, emb, h)."""
   return _abs_terms(P, x_nhwc, masks, gout, gout_abs, taus)
+
+
+# ------------------------------------------------------------- one layer against float64
+# The per-layer form of the measures above: one layer (its input, weights, bias and the
+# gradient of its pre-activation all given by the caller -- a device test passes the device's
+# own input to the layer, so the layer is judged alone and its ReLU decision, in > 0, is
+# exactly the one the device's mask epilogue reads), every result with the float64 sum of the
+# absolute values of the terms its reduction adds.  COND_FLOOR and LAYER_TOL restate
+# tests/test_gpu_northstar.py's COND_FLOOR and GRAD_TOL / MASK_TOL: the same measure, the
+# same bar.
+COND_FLOOR = 1e-3
+LAYER_TOL = 1e-5
+LAYERS = ('conv1', 'conv2', 'conv3', 'fc1', 'fc2')
+
+
+def _f64(t):
+  return torch.as_tensor(t).detach().to('cpu', torch.float64)
+
+
+def layer_reference(layer, x_in, w, b, dz, pad=None):
+  """float64 forward and backward of one layer.
+
+  layer: one of LAYERS.  x_in: the layer's input as the device keeps it (NHWC for a
+  convolution, (B, features) for fc1 -- conv3's output in TF's flatten order -- and fc2).
+  w, b: the weights in torch layout ((out, in, kh, kw) / (out, in)) and the bias.  dz: the
+  gradient of the layer's pre-activation, in the layer's output layout.  pad: another
+  (left, right, top, bottom) padding for a convolution (a deliberately wrong reference).
+
+  Returns a dict of float64 tensors, each result beside its Σ|terms| (suffix _abs):
+    z, z_abs      the pre-activation and Σ|w||in| + |b|, in the output layout (NHWC)
+    dx, dx_abs    (Wᵀ dz) · (in > 0) and Σ|w||dz| (masked alike), in the input layout
+    dw, dw_abs    the weight gradient and Σ|dz||in|, flat (out, kh, kw, in) / (out, in)
+    db, db_abs    the bias gradient and Σ|dz|."""
+  x_in, w, b, dz = _f64(x_in), _f64(w), _f64(b), _f64(dz)
+  B = x_in.shape[0]
+  if layer in _CONVS:
+    p, stride, ishape, oshape = _CONVS[layer]
+    fn = _conv(p if pad is None else pad, stride)
+    to_in = lambda t: t.reshape((B,) + ishape).permute(0, 3, 1, 2)
+    to_out = lambda t: t.reshape((B,) + oshape).permute(0, 3, 1, 2)
+    from_in = lambda t: t.permute(0, 2, 3, 1).reshape(x_in.shape)
+    from_out = lambda t: t.permute(0, 2, 3, 1)
+    flat_w = lambda t: t.permute(0, 2, 3, 1).reshape(-1)
+    sum_b = lambda t: t.sum(dim=(0, 2, 3))
+  else:
+    assert layer in ('fc1', 'fc2') and pad is None, layer
+    fn = lambda xs, w_, b_: F.linear(xs[0], w_, b_)
+    to_in = to_out = from_in = from_out = lambda t: t.reshape(B, -1)
+    flat_w = lambda t: t.reshape(-1)
+    sum_b = lambda t: t.sum(0)
+  x, g = to_in(x_in), to_out(dz)
+
+  def grads(xv, wv, gv):
+    xv = xv.clone().requires_grad_(True)
+    wv = wv.clone().requires_grad_(True)
+    fn([xv], wv, None).backward(gv)
+    return xv.grad, wv.grad
+
+  with torch.no_grad():
+    z = fn([x], w, b)
+    z_abs = fn([x.abs()], w.abs(), b.abs())
+  dx, dw = grads(x, w, g)
+  dx_abs, dw_abs = grads(x.abs(), w.abs(), g.abs())
+  keep = (x > 0).to(torch.float64)
+  return dict(z=from_out(z), z_abs=from_out(z_abs),
+              dx=from_in(dx * keep), dx_abs=from_in(dx_abs * keep),
+              dw=flat_w(dw), dw_abs=flat_w(dw_abs), db=sum_b(g), db_abs=sum_b(g.abs()))
+
+
+def cond_ratio(got, ref, terms):
+  """|got - ref| / max(Σ|terms|, COND_FLOOR · max|ref|), element by element (float64)."""
+  got, ref, terms = _f64(got), _f64(ref), _f64(terms)
+  assert got.shape == ref.shape == terms.shape, (got.shape, ref.shape, terms.shape)
+  den = torch.clamp(torch.maximum(terms, COND_FLOOR * ref.abs().max()), min=1e-300)
+  return (got - ref).abs() / den
+
+
+def assert_layer_close(what, got, ref, terms, tol=LAYER_TOL):
+  """The one assertion of the per-layer tests: every element finite and within ``tol`` on
+  cond_ratio.  Prints and returns the worst ratio."""
+  got = _f64(got)
+  assert bool(torch.isfinite(got).all()), '%s: not finite' % what
+  r = cond_ratio(got, ref, terms)
+  worst = float(r.max()) if r.numel() else 0.0
+  print('%s: worst ratio %.3g' % (what, worst))
+  assert worst <= tol, '%s: ratio %.3g at flat index %d, over %.1g' % (what, worst,
+                                                                     int(r.argmax()), tol)
+  return worst
+
+
+def assert_spare_untouched(what, buf, batch):
+  """A buffer driven at ``batch`` samples must hold one more, still NaN.  A buffer without
+  the spare sample fails: an empty slice would otherwise pass for an untouched one."""
+  assert buf.shape[0] == batch + 1, '%s: %d samples, no spare one past %d' % (what, buf.shape[0],
+                                                                            batch)
+  assert bool(torch.isnan(buf[batch:]).all()), '%s: sample %d was written' % (what, batch)
+
+
+def assert_guard_untouched(what, ws, need, guard=64):
+  """A workspace of ``need`` floats must be followed by ``guard`` floats, still NaN."""
+  assert ws.numel() == need + guard, '%s: %d floats, not %d + %d guard words' % (
+      what, ws.numel(), need, guard)
+  assert bool(torch.isnan(ws[need:]).all()), '%s: guard words were written' % what

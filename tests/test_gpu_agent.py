@@ -22,18 +22,18 @@ def _fill(mem, A, seed):
                   priorities=rs.uniform(0.1, 2.0, C) if mem._prioritized else None)
 
 
-def _rainbow(**kw):
+def _rainbow(num_actions=9, **kw):
   from dopamine_amd.agents.optimizers import AdamOptimizer
   from dopamine_amd.agents.rainbow.rainbow_agent import RainbowAgent
-  a = RainbowAgent(num_actions=9, update_horizon=3, replay_capacity=3000, batch_size=32,
+  a = RainbowAgent(num_actions=num_actions, update_horizon=3, replay_capacity=3000, batch_size=32,
                    min_replay_history=100, optimizer=AdamOptimizer(6.25e-5, epsilon=1.5e-4), **kw)
-  _fill(a._replay.memory, 9, 3)
+  _fill(a._replay.memory, num_actions, 3)
   return a
 
 
-def test_rainbow_step_matches_cpu_restatement():
+def _rainbow_step_matches_cpu_restatement(A):
   random.seed(11)
-  a = _rainbow(use_hip_graph=False)
+  a = _rainbow(A, use_hip_graph=False)
   w0 = a.online_convnet.fp.flat.detach().cpu().clone()
   tw = a.target_convnet.fp.flat.detach().cpu().clone()
   a._run_train_op()
@@ -41,8 +41,8 @@ def test_rainbow_step_matches_cpu_restatement():
   t = {k: v.detach().cpu() for k, v in a._replay.transition.items()}
   # CPU restatement on the same batch and weights
   from dopamine_amd.agents.networks import RainbowNetwork
-  on = RainbowNetwork(9, device='cpu'); on.fp.flat.copy_(w0)
-  tg = RainbowNetwork(9, device='cpu'); tg.fp.flat.copy_(tw)
+  on = RainbowNetwork(A, device='cpu'); on.fp.flat.copy_(w0)
+  tg = RainbowNetwork(A, device='cpu'); tg.fp.flat.copy_(tw)
   with torch.no_grad():
     tl = tg(t['next_state']).double().numpy()
   logits = on(t['state'])
@@ -63,15 +63,27 @@ def test_rainbow_step_matches_cpu_restatement():
   np.testing.assert_allclose(pri, np.sqrt(exp['loss'] + 1e-10), rtol=1e-4)
 
 
-@pytest.mark.parametrize('kind', ['rainbow', 'dqn', 'iqn'])
+def test_rainbow_step_matches_cpu_restatement():
+  _rainbow_step_matches_cpu_restatement(9)
+
+
+@pytest.mark.parametrize('num_actions', [16, 18])
+def test_rainbow_step_matches_cpu_restatement_at(num_actions):
+  """The same with 16 actions and with the full 18-action set (n_out = 918: fc2's input
+  gradient in two K slices, the fused loss's 16 waves over 18 actions)."""
+  _rainbow_step_matches_cpu_restatement(num_actions)
+
+
+# ('rainbow16', 'rainbow18': Rainbow with 16 / 18 actions instead of 9)
+@pytest.mark.parametrize('kind', ['rainbow', 'dqn', 'iqn', 'rainbow16', 'rainbow18'])
 def test_hip_graph_replay_matches_eager(kind):
   from dopamine_amd.agents.dqn.dqn_agent import DQNAgent
   from dopamine_amd.agents.implicit_quantile.implicit_quantile_agent import ImplicitQuantileAgent
 
   def make(graph):
     random.seed(5); np.random.seed(5); torch.manual_seed(5)
-    if kind == 'rainbow':
-      return _rainbow(use_hip_graph=graph)
+    if kind.startswith('rainbow'):
+      return _rainbow(int(kind[7:] or 9), use_hip_graph=graph)
     if kind == 'dqn':
       a = DQNAgent(num_actions=6, replay_capacity=3000, batch_size=32, min_replay_history=100,
                    use_hip_graph=graph)

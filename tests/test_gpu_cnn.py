@@ -15,7 +15,8 @@ def _close(a, b, rtol=2e-5):
   assert err <= rtol * scale, 'max err %.3g vs scale %.3g' % (err, scale)
 
 
-@pytest.mark.parametrize('kind,B,A', [('rainbow', 32, 9), ('dqn', 32, 6), ('rainbow', 7, 4)])
+@pytest.mark.parametrize('kind,B,A', [('rainbow', 32, 9), ('dqn', 32, 6), ('rainbow', 7, 4),
+                                        ('rainbow', 33, 18), ('dqn', 1, 1)])
 def test_hip_cnn_matches_torch(kind, B, A):
   from dopamine_amd.agents.networks import NatureDQNNetwork, RainbowNetwork
   from dopamine_amd.cnn import HipNatureCNN
@@ -75,19 +76,17 @@ def test_hip_cnn_graph_capturable_and_deterministic():
   assert torch.equal(net.fp.grad, ref_g)     # split-K reduced in fixed order: bitwise stable
 
 
-def test_fused_adam_backward_equals_backward_then_adam():
-  """dq_cnn_backward_adam == dq_cnn_backward + dq_adam_tf1, bitwise, over two
-  steps (both beta-power slots): same gradient, same ApplyAdam arithmetic."""
+def _fused_adam_backward_equals_backward_then_adam(B, A):
   from dopamine_amd import ops
   from dopamine_amd.agents.networks import RainbowNetwork
   from dopamine_amd.cnn import HipNatureCNN
-  nets = [RainbowNetwork(9, device='cuda', seed=5) for _ in range(2)]
-  hips = [HipNatureCNN(n, 32) for n in nets]
+  nets = [RainbowNetwork(A, device='cuda', seed=5) for _ in range(2)]
+  hips = [HipNatureCNN(n, B) for n in nets]
   opts = [ops.TF1Adam(n.fp.flat, learning_rate=6.25e-5, epsilon=1.5e-4) for n in nets]
   torch.manual_seed(1)
   for step in range(2):
-    x = torch.rand(32, 84, 84, 4, device='cuda')
-    gout = torch.randn(32, 459, device='cuda')
+    x = torch.rand(B, 84, 84, 4, device='cuda')
+    gout = torch.randn(B, A * 51, device='cuda')
     for h in hips:
       h.forward(x)
     hips[0].backward(gout, adam=opts[0], slot=step % 2)
@@ -100,11 +99,26 @@ def test_fused_adam_backward_equals_backward_then_adam():
       assert torch.equal(getattr(opts[0], n), getattr(opts[1], n)), (step, n)
 
 
-@pytest.mark.parametrize('B', [32, 7])
-def test_forward_pair_equals_two_forwards(B):
+def test_fused_adam_backward_equals_backward_then_adam():
+  """dq_cnn_backward_adam == dq_cnn_backward + dq_adam_tf1, bitwise, over two
+  steps (both beta-power slots): same gradient, same ApplyAdam arithmetic."""
+  _fused_adam_backward_equals_backward_then_adam(32, 9)
+
+
+@pytest.mark.parametrize('B,A', [(33, 18), (1, 4)])
+def test_fused_adam_backward_equals_backward_then_adam_at_edges(B, A):
+  """The same at (33, 18) -- fc2's fused-optimizer epilogue over 918 rows (seven 128-row
+  tiles and a ragged eighth) with K = B = 33 -- and at batch 1."""
+  _fused_adam_backward_equals_backward_then_adam(B, A)
+
+
+# (B, A): the first cases keep the ids they had when B was the only parameter
+@pytest.mark.parametrize('B,A', [pytest.param(32, 9, id='32'), pytest.param(7, 9, id='7'),
+                                 (33, 18), (1, 9)])
+def test_forward_pair_equals_two_forwards(B, A):
   from dopamine_amd.agents.networks import RainbowNetwork
   from dopamine_amd.cnn import HipNatureCNN, forward_pair
-  on, tg = RainbowNetwork(9, device='cuda', seed=1), RainbowNetwork(9, device='cuda', seed=2)
+  on, tg = RainbowNetwork(A, device='cuda', seed=1), RainbowNetwork(A, device='cuda', seed=2)
   ho, ht = HipNatureCNN(on, B), HipNatureCNN(tg, B)
   x, nx = torch.rand(B, 84, 84, 4, device='cuda'), torch.rand(B, 84, 84, 4, device='cuda')
   ref_o, ref_t = ho.forward(x).clone(), ht.forward(nx).clone()
@@ -115,14 +129,15 @@ def test_forward_pair_equals_two_forwards(B):
   assert torch.equal(yo, ref_o) and torch.equal(yt, ref_t)
 
 
-@pytest.mark.parametrize('B', [32, 5])
-def test_forward_head_and_tail_equal_forward(B):
+@pytest.mark.parametrize('B,A', [pytest.param(32, 9, id='32'), pytest.param(5, 9, id='5'),
+                                 (33, 18), (1, 9)])
+def test_forward_head_and_tail_equal_forward(B, A):
   """Head (eager, or riding in another net's backward) + tail (in the other net's
   forward) == forward(), bit for bit; the backward's own gradients are unchanged
   by the riding head."""
   from dopamine_amd.agents.networks import RainbowNetwork
   from dopamine_amd.cnn import HipNatureCNN, forward_with_tail
-  on, tg = RainbowNetwork(9, device='cuda', seed=1), RainbowNetwork(9, device='cuda', seed=2)
+  on, tg = RainbowNetwork(A, device='cuda', seed=1), RainbowNetwork(A, device='cuda', seed=2)
   ho, ht = HipNatureCNN(on, B), HipNatureCNN(tg, B)
   x, nx = torch.rand(B, 84, 84, 4, device='cuda'), torch.rand(B, 84, 84, 4, device='cuda')
   ref_o, ref_t = ho.forward(x).clone(), ht.forward(nx).clone()
@@ -145,7 +160,7 @@ def test_forward_head_and_tail_equal_forward(B):
   assert torch.equal(yo, ref_o) and torch.equal(yt, ref_t)
 
 
-@pytest.mark.parametrize('B,A', [(32, 9), (7, 4)])
+@pytest.mark.parametrize('B,A', [(32, 9), (7, 4), (33, 18), (5, 16), (1, 4)])
 def test_fused_forward_and_c51_equal_separate_path(B, A):
   """The Rainbow fast path: forward_fused's fc2 k-band partials summed by
   c51_loss_fused give bitwise dq_cnn_forward's logits (written out on request)
@@ -215,7 +230,17 @@ def test_fused_forward_and_c51_equal_separate_path(B, A):
   # head_from = 8: the target net one launch ahead (conv1 in the backward as for 6) and
   # the C51 loss split -- its target half riding beside the online fused head, the loss
   # launch the online half: loss, gradient, priorities and d h bitwise the one kernel's
+  # (at most 16 actions -- (5, 16) is the last size; with 18 the call is refused with the
+  # header's argument error before anything is launched, and an agent stays on head_from 6)
+  from dopamine_amd import _lib
   from dopamine_amd.cnn import forward_fused_c51
+  if A > 16:
+    m = torch.full((B, N), float('nan'), device='cuda')
+    with pytest.raises(_lib.DQError, match='at most 16 actions'):
+      forward_fused_c51(ho, x, ht, rew, term, sup, 0.970299, m)
+    torch.cuda.synchronize()
+    assert torch.isnan(m).all()
+    return
   ho.dacts['h'].copy_(dh0)
   ho.backward(got['grad'].view(B, -1), groups=(1, 7), head=(ht, nx2), head_from=6)
   forward_fused(ho, x, ht, conv3_b=True, conv2_b=True)
@@ -241,22 +266,37 @@ def test_fused_forward_and_c51_equal_separate_path(B, A):
   assert torch.equal(ho.dacts['h'], dh6)
 
 
-@pytest.mark.parametrize('centered', [True, False])
-def test_fused_rmsprop_backward_equals_backward_then_rmsprop(centered):
+@pytest.mark.parametrize('A,head_from', [(16, 8), (18, 6)])
+def test_fused_rainbow_agent_splits_the_c51_loss_up_to_16_actions(A, head_from):
+  """RainbowAgent's schedule choice follows dq_cnn_forward_fused_c51's limit: with split_c51
+  a fused agent takes head_from 8 at 16 actions and falls back to 6 at 18."""
+  from dopamine_amd.agents.optimizers import AdamOptimizer
+  from dopamine_amd.agents.rainbow.rainbow_agent import RainbowAgent
+  a = RainbowAgent(num_actions=A, update_horizon=3, replay_capacity=3000, batch_size=32,
+                   min_replay_history=100, optimizer=AdamOptimizer(6.25e-5, epsilon=1.5e-4))
+  assert a._fused() and a._head_from() == 6          # split_c51 is off by default
+  a.split_c51 = True
+  assert a._head_from() == head_from
+
+
+# (centered, B, A): the first two cases keep the ids they had when centered was the only parameter
+@pytest.mark.parametrize('centered,B,A', [pytest.param(True, 32, 6, id='True'),
+                                          pytest.param(False, 32, 6, id='False'), (True, 5, 1)])
+def test_fused_rmsprop_backward_equals_backward_then_rmsprop(centered, B, A):
   """The backward with TF1 RMSProp spread over its launches (dq_adam_args kind
   DQ_OPT_RMSPROP) == dq_cnn_backward + dq_rmsprop_tf1, bitwise, over two steps, for
   the seven-launch schedule and the fused head's six-launch one (head_from 6)."""
   from dopamine_amd import ops
   from dopamine_amd.agents.networks import NatureDQNNetwork
   from dopamine_amd.cnn import HipNatureCNN
-  nets = [NatureDQNNetwork(6, device='cuda', seed=5) for _ in range(2)]
-  hips = [HipNatureCNN(n, 32) for n in nets]
+  nets = [NatureDQNNetwork(A, device='cuda', seed=5) for _ in range(2)]
+  hips = [HipNatureCNN(n, B) for n in nets]
   opts = [ops.TF1RMSProp(n.fp.flat, learning_rate=2.5e-4, decay=0.95, momentum=0.1,
                          epsilon=1e-5, centered=centered) for n in nets]
   torch.manual_seed(1)
   for step, groups in enumerate([None, (0, 7), None]):
-    x = torch.rand(32, 84, 84, 4, device='cuda')
-    gout = torch.randn(32, 6, device='cuda')
+    x = torch.rand(B, 84, 84, 4, device='cuda')
+    gout = torch.randn(B, A, device='cuda')
     for h in hips:
       h.forward(x)
     if groups is None:
@@ -273,7 +313,7 @@ def test_fused_rmsprop_backward_equals_backward_then_rmsprop(centered):
         assert torch.equal(getattr(opts[0], n)[o:o + m], getattr(opts[1], n)[o:o + m]), (step, n)
 
 
-@pytest.mark.parametrize('B,A', [(32, 6), (7, 18)])
+@pytest.mark.parametrize('B,A', [(32, 6), (7, 18), (33, 129), (1, 1)])
 def test_fused_forward_and_dqn_loss_equal_separate_path(B, A):
   """The DQN fast path: forward_fused's fc2 partials summed by dqn_huber_loss_fused give
   bitwise dq_cnn_forward's Q-values and therefore bitwise dq_dqn_huber_loss's gradient
@@ -305,6 +345,24 @@ def test_fused_forward_and_dqn_loss_equal_separate_path(B, A):
   for t in (ho.acts['out'], ht.acts['out'], ho.acts['h'], ho.dacts['h']):
     t.fill_(float('nan'))
   forward_fused(ho, x, ht)
+  if A > 64:
+    # (33, 129): the fused head's second group of fc2 column tiles (one column) and second
+    # row tile (one row).  The fused loss kernel takes at most 64 actions (the header's
+    # documented limit) and refuses this width, so its part of the check -- the k-band
+    # partials summed in band order plus the bias -- is done here in fp32 on the host side
+    from dopamine_amd import _lib
+    from dopamine_amd.cnn import fc2_parts
+    with pytest.raises(_lib.DQError, match='num_actions'):
+      ops.dqn_huber_loss_fused(ho, ht, act, rew, term, 0.99, q_out=True)
+    torch.cuda.synchronize()
+    assert torch.equal(ho.acts['h'], ref_h)
+    for hip, net, ref_y in ((ho, on, ref_o), (ht, tg, ref_t)):
+      parts = fc2_parts(hip)
+      y = parts[0].clone()
+      for j in range(1, parts.shape[0]):
+        y = y + parts[j]
+      assert torch.equal(y + net.fp.params['fc2_b'], ref_y)
+    return
   got = ops.dqn_huber_loss_fused(ho, ht, act, rew, term, 0.99, q_out=True)
   torch.cuda.synchronize()
   assert torch.equal(ho.acts['h'], ref_h)
@@ -320,18 +378,15 @@ def test_fused_forward_and_dqn_loss_equal_separate_path(B, A):
   assert torch.equal(torch.cat([v.reshape(-1) for v in on.fp.grad_views]), ref_g)
 
 
-def test_grouped_torso_backward_equals_per_layer_bitwise():
-  """dq_cnn_backward_torso (IQN's torso: conv3 .. conv1 from d a3) in its four grouped
-  launches == the per-layer launches of the same tiles (dq_cnn_backward_layer), bit for bit:
-  every conv weight / bias gradient and the input gradients d a2, d a1."""
+def _grouped_torso_backward_equals_per_layer_bitwise(B):
   import ctypes
   from dopamine_amd import _lib
   from dopamine_amd.agents.networks import RainbowNetwork
   from dopamine_amd.cnn import HipNatureCNN
   torch.manual_seed(3)
   net = RainbowNetwork(9, device='cuda', seed=2)
-  hip = HipNatureCNN(net, 32)
-  x = torch.rand(32, 84, 84, 4, device='cuda')
+  hip = HipNatureCNN(net, B)
+  x = torch.rand(B, 84, 84, 4, device='cuda')
   hip.forward(x)
   da3 = torch.randn_like(hip.dacts['a3']) * (hip.acts['a3'] > 0)
   stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -344,12 +399,12 @@ def test_grouped_torso_backward_equals_per_layer_bitwise():
     hip.dacts['a1'].fill_(float('nan'))
     if grouped:
       _lib.check(_lib.lib.dq_cnn_backward_torso(
-          ctypes.byref(hip._p), ctypes.byref(hip._g), 32, hip._x.data_ptr(), ctypes.byref(hip._a),
+          ctypes.byref(hip._p), ctypes.byref(hip._g), B, hip._x.data_ptr(), ctypes.byref(hip._a),
           ctypes.byref(hip._d), hip.ws.data_ptr(), stream), 'dq_cnn_backward_torso')
     else:
       for layer, part in ((2, 1), (2, 0), (3, 1), (3, 0), (4, 1)):
         _lib.check(_lib.lib.dq_cnn_backward_layer(
-            ctypes.byref(hip._p), ctypes.byref(hip._g), 32, hip._x.data_ptr(),
+            ctypes.byref(hip._p), ctypes.byref(hip._g), B, hip._x.data_ptr(),
             ctypes.byref(hip._a), hip.dacts['a3'].data_ptr(), ctypes.byref(hip._d),
             hip.ws.data_ptr(), layer, part, stream), 'dq_cnn_backward_layer')
     torch.cuda.synchronize()
@@ -364,3 +419,17 @@ def test_grouped_torso_backward_equals_per_layer_bitwise():
     assert torch.isfinite(ga[n]).all(), n
     assert torch.equal(ga[n], gb[n]), n
   assert torch.equal(a2a, a2b) and torch.equal(a1a, a1b)
+
+
+def test_grouped_torso_backward_equals_per_layer_bitwise():
+  """dq_cnn_backward_torso (IQN's torso: conv3 .. conv1 from d a3) in its four grouped
+  launches == the per-layer launches of the same tiles (dq_cnn_backward_layer), bit for bit:
+  every conv weight / bias gradient and the input gradients d a2, d a1."""
+  _grouped_torso_backward_equals_per_layer_bitwise(32)
+
+
+@pytest.mark.parametrize('B', [1, 5, 33, 64])
+def test_grouped_torso_backward_equals_per_layer_bitwise_at_batch(B):
+  """The same where the split-K weight gradients change shape: one slab (B = 1), a ragged
+  second conv2 / conv3 slab (5), conv1's chunk of two K slices (33), and 64."""
+  _grouped_torso_backward_equals_per_layer_bitwise(B)
