@@ -765,6 +765,11 @@ int dq_c51_loss_fused(const float* online_parts, const float* online_bias,
   DQ_CHECK_ARG(num_atoms >= 2 && num_atoms <= 64, "num_atoms must be in [2, 64]");
   DQ_CHECK_ARG(batch >= 1 && num_actions >= 1 && num_actions <= 256, "bad batch / num_actions");
   DQ_CHECK_ARG(!fc2_w || (h && dh && hidden >= 1), "d h needs h, dh and hidden");
+  // the W2 rows reach LDS as 16-byte chunks of a row slice: a row that is no whole number of
+  // chunks would be packed at another stride than dh_dot reads, from unaligned addresses
+  DQ_CHECK_ARG(!fc2_w || hidden % 4 == 0, "d h needs hidden to be a multiple of 4");
+  DQ_CHECK_ARG(!fc2_w || ((uintptr_t)fc2_w | (uintptr_t)h | (uintptr_t)dh) % 16 == 0,
+               "fc2_w, h and dh must be 16-byte aligned");
   C51Args a{nullptr, nullptr, actions, rewards, terminals, probs, support, batch, num_actions,
             num_atoms, cumulative_gamma, grad_logits, loss_out, priorities_out, nullptr};
   const int NO = num_actions * num_atoms;
@@ -798,6 +803,11 @@ int dq_c51_loss_online(const float* online_parts, const float* online_bias, int3
   DQ_CHECK_ARG(num_atoms >= 2 && num_atoms <= 64, "num_atoms must be in [2, 64]");
   DQ_CHECK_ARG(batch >= 1 && num_actions >= 1 && num_actions <= 64, "bad batch / num_actions");
   DQ_CHECK_ARG(!fc2_w || (h && dh && hidden >= 1), "d h needs h, dh and hidden");
+  // the N x hidden block of W2 reaches LDS linearly in 16-byte chunks: whole chunks, from
+  // 16-byte aligned addresses, need hidden % 4 == 0 (then (N * hidden) % 4 == 0 too)
+  DQ_CHECK_ARG(!fc2_w || hidden % 4 == 0, "d h needs hidden to be a multiple of 4");
+  DQ_CHECK_ARG(!fc2_w || ((uintptr_t)fc2_w | (uintptr_t)h | (uintptr_t)dh) % 16 == 0,
+               "fc2_w, h and dh must be 16-byte aligned");
   C51Args a{nullptr, nullptr, actions, nullptr, nullptr, probs, nullptr, batch, num_actions,
             num_atoms, 0.0f, grad_logits, loss_out, priorities_out, nullptr};
   const int NO = num_actions * num_atoms;

@@ -260,7 +260,10 @@ int dq_c51_loss(const float* online_logits, const float* target_logits, const in
 /* The online half of dq_c51_loss_fused (rainbow_agent.py:253-305: softmax cross-entropy of
    the chosen online logits against the projected target distribution, PER weights, new
    priorities, dlogits and d h) given target_m (B, num_atoms) from dq_cnn_forward_fused_c51;
-   loss, gradient, priorities and d h are bitwise dq_c51_loss_fused's. */
+   loss, gradient, priorities and d h are bitwise dq_c51_loss_fused's.  num_actions <= 64,
+   2 <= num_atoms <= 64.  With fc2_w set (d h wanted): hidden a multiple of 4, fc2_w, h and dh
+   16-byte aligned, and num_atoms * hidden floats within the LDS (160 KB, less the head);
+   anything else is refused with DQ_E_ARG before a launch. */
 int dq_c51_loss_online(const float* online_parts, const float* online_bias, int32_t n_parts,
                        const float* target_m, const int32_t* actions, const float* probs,
                        int32_t batch, int32_t num_actions, int32_t num_atoms, float* grad_logits,
@@ -271,7 +274,11 @@ int dq_c51_loss_online(const float* online_parts, const float* online_bias, int3
    partial slabs [n_parts][B][A*N] summed in order + bias (bitwise dq_cnn_forward's logits,
    written to *_logits_out when non-NULL); with fc2_w set it also writes the fc2 input
    gradient dh = (grad_logits . fc2_w) * (h > 0), (B, hidden), so the CNN backward can start
-   at its launch 1.  The mean-loss summary is not produced here. */
+   at its launch 1.  num_actions <= 64, 2 <= num_atoms <= 64.  With fc2_w set: hidden a
+   multiple of 4 (a multiple of 16 splits d h over four blocks per sample), fc2_w, h and dh
+   16-byte aligned, and num_atoms * hidden floats (a quarter of them when split) within the
+   LDS (160 KB, less the head); anything else is refused with DQ_E_ARG before a launch.
+   The mean-loss summary is not produced here. */
 int dq_c51_loss_fused(const float* online_parts, const float* online_bias,
                       const float* target_parts, const float* target_bias, int32_t n_parts,
                       const int32_t* actions, const float* rewards, const uint8_t* terminals,

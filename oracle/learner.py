@@ -73,8 +73,70 @@ def c51_loss(online_logits, target_logits, actions, rewards, terminals, support,
   # grad_abs: the magnitudes of the difference's two terms (oracle/nature_cnn.abs_grad)
   grad_abs = np.zeros_like(ol)
   grad_abs[np.arange(B), actions] = (w / B)[:, None] * (sm + proj)
+  priorities = np.sqrt(loss + dtype(1e-10))
+  # The projection-aware term sums (float64 whatever ``dtype``), for the loss kernels' own
+  # tests: grad_abs above takes proj as exact, but every clipped quotient
+  # 1 - |clip(Tz_j) - z_i| / dz is a difference of quantities of size
+  # (|r| + gamma_t |z_j| + |z_i|) / dz, far above its value near the support's ends.
+  f8 = np.float64
+  pabs = projection_terms(rewards, gamma_t, tp[np.arange(B), astar], z)
+  ch8 = chosen.astype(f8)
+  sm_terms = sm.astype(f8) * (1 + np.abs(ch8 - ch8.max(1, keepdims=True)))
+  gabs_proj = np.zeros(ol.shape, f8)
+  gabs_proj[np.arange(B), actions] = (w.astype(f8) / B)[:, None] * (sm_terms + pabs)
+  loss_abs = (pabs * (np.abs(lse.astype(f8))[:, None] + np.abs(ch8))).sum(1)
   return dict(loss=loss, weights=w, grad=grad, grad_abs=grad_abs, proj=proj, argmax=astar,
-              priorities=np.sqrt(loss + dtype(1e-10)), mean_loss=(w * loss).mean())
+              priorities=priorities, mean_loss=(w * loss).mean(),
+              proj_abs=pabs, grad_abs_proj=gabs_proj, loss_abs=loss_abs,
+              prio_abs=loss_abs / (2 * priorities.astype(f8)))
+
+
+def c51_cross_entropy(online_logits, target_m, actions, probs=None, dtype=np.float64):
+  """The online half of c51_loss given the projected target distribution ``target_m`` (B, N)
+  (rainbow_agent.py:253-305): the same keys, the term sums taking target_m as exact."""
+  ol = np.asarray(online_logits, dtype)
+  m = np.asarray(target_m, dtype)
+  B = ol.shape[0]
+  rows = np.arange(B)
+  chosen = ol[rows, actions]
+  sm = softmax(chosen)
+  lse = np.log(np.exp(chosen - chosen.max(1, keepdims=True)).sum(1)) + chosen.max(1)
+  loss = (m * (lse[:, None] - chosen)).sum(1)
+  if probs is not None:
+    w = 1.0 / np.sqrt(np.asarray(probs, dtype) + dtype(1e-10))
+    w = w / w.max()
+  else:
+    w = np.ones(B, dtype)
+  grad = np.zeros_like(ol)
+  grad[rows, actions] = (w / B)[:, None] * (sm - m)
+  priorities = np.sqrt(loss + dtype(1e-10))
+  f8 = np.float64
+  ch8 = chosen.astype(f8)
+  gabs = np.zeros(ol.shape, f8)
+  gabs[rows, actions] = (w.astype(f8) / B)[:, None] * (
+      sm.astype(f8) * (1 + np.abs(ch8 - ch8.max(1, keepdims=True))) + np.abs(m.astype(f8)))
+  loss_abs = (np.abs(m.astype(f8)) * (np.abs(lse.astype(f8))[:, None] + np.abs(ch8))).sum(1)
+  return dict(loss=loss, weights=w, grad=grad, priorities=priorities, mean_loss=(w * loss).mean(),
+              grad_abs_proj=gabs, loss_abs=loss_abs, prio_abs=loss_abs / (2 * priorities.astype(f8)))
+
+
+def projection_terms(rewards, gamma_t, weights, support, reach=1e-3):
+  """Σ|terms| of project_distribution, float64 (B, N): for target atom i the sum over the
+  source atoms j whose clipped quotient can be non-zero (|clip(Tz_j) - z_i| / dz < 1 + reach)
+  of p_j (1 + (mag_j + |z_i|) / dz), with mag_j = |r| + gamma_t |z_j| where Tz_j is inside
+  the support and max(|vmin|, |vmax|) where it is clipped (the clipped value is exact)."""
+  f8 = np.float64
+  z = np.asarray(support, f8)
+  r = np.asarray(rewards, f8)[:, None]
+  g = np.asarray(gamma_t, f8)[:, None]
+  p = np.asarray(weights, f8)
+  dz = z[1] - z[0]
+  tz = r + g * z[None, :]                                           # (B, N) over j
+  clipped = np.clip(tz, z[0], z[-1])
+  mag = np.where(clipped != tz, max(abs(z[0]), abs(z[-1])), np.abs(r) + g * np.abs(z)[None, :])
+  near = np.abs(clipped[:, None, :] - z[None, :, None]) / dz < 1 + reach   # (B, i, j)
+  term = p[:, None, :] * (1 + (mag[:, None, :] + np.abs(z)[None, :, None]) / dz)
+  return (term * near).sum(-1)
 
 
 def dqn_huber(online_q, target_q, actions, rewards, terminals, cumulative_gamma,
@@ -94,7 +156,17 @@ def dqn_huber(online_q, target_q, actions, rewards, terminals, cumulative_gamma,
   grad[np.arange(B), actions] = np.clip(err, -delta, delta) / B
   grad_abs = np.zeros_like(oq)       # |q| + |target| of the difference err (abs_grad)
   grad_abs[np.arange(B), actions] = (np.abs(chosen) + np.abs(target)) / B
-  return dict(loss=loss, grad=grad, grad_abs=grad_abs, target=target, mean_loss=loss.mean())
+  loss_abs = _huber_terms(a, np.abs(chosen) + np.abs(target), delta)
+  return dict(loss=loss, grad=grad, grad_abs=grad_abs, target=target, mean_loss=loss.mean(),
+              loss_abs=loss_abs)
+
+
+def _huber_terms(au, mag, delta):
+  """Σ|terms| of the Huber loss of a difference u whose two operands sum to ``mag`` in
+  magnitude (float64): the quadratic branch u u / 2 moves by |u| per unit of u, the linear
+  one delta (|u| - delta / 2) by delta."""
+  au, mag = np.asarray(au, np.float64), np.asarray(mag, np.float64)
+  return np.where(au <= delta, au * mag + 0.5 * au * au, delta * (mag + 0.5 * delta))
 
 
 def iqn_loss(online_qv, target_qv, target_qv_action, taus, actions, rewards, terminals,
@@ -135,8 +207,11 @@ def iqn_loss(online_qv, target_qv, target_qv_action, taus, actions, rewards, ter
   dabs = np.where(au <= kappa, np.abs(T)[:, :, None] + np.abs(theta)[:, None, :], kappa)
   gabs = np.zeros_like(oq).reshape(N, B, A)
   gabs[:, np.arange(B), actions] = ((w * dabs / kappa).sum(1) / Np / B).T
+  # loss_abs: every term w |T - theta|-Huber / kappa at its operands' magnitudes |T| + |theta|
+  habs = _huber_terms(au, np.abs(T)[:, :, None] + np.abs(theta)[:, None, :], kappa)
+  loss_abs = (w.astype(np.float64) * habs / kappa).sum(2).mean(1)
   return dict(loss=loss, grad=grad.reshape(N * B, A), grad_abs=gabs.reshape(N * B, A),
-              mean_loss=loss.mean(), argmax=astar)
+              mean_loss=loss.mean(), argmax=astar, loss_abs=loss_abs)
 
 
 class TF1Adam:
@@ -166,12 +241,14 @@ class TF1Adam:
 
 
 class TF1CenteredRMSProp:
-  """tf.train.RMSPropOptimizer(centered=True) / ApplyCenteredRMSProp.
+  """tf.train.RMSPropOptimizer / ApplyCenteredRMSProp (centered=True) or ApplyRMSProp
+  (centered=False: denom = ms + eps, mg unused).
 
   rms slot initialised to ONE (TF1), mg and mom to zero."""
 
-  def __init__(self, n, lr, decay=0.9, momentum=0.0, eps=1e-10, dtype=np.float32):
+  def __init__(self, n, lr, decay=0.9, momentum=0.0, eps=1e-10, dtype=np.float32, centered=True):
     self.dt = dtype
+    self.centered = bool(centered)
     self.lr, self.rho, self.mu, self.eps = (dtype(x) for x in (lr, decay, momentum, eps))
     self.ms = np.ones(n, dtype)
     self.mg = np.zeros(n, dtype)
@@ -180,8 +257,11 @@ class TF1CenteredRMSProp:
   def step(self, var, g):
     one = self.dt(1)
     self.ms += (g * g - self.ms) * (one - self.rho)
-    self.mg += (g - self.mg) * (one - self.rho)
-    denom = self.ms - self.mg * self.mg + self.eps
+    if self.centered:
+      self.mg += (g - self.mg) * (one - self.rho)
+      denom = self.ms - self.mg * self.mg + self.eps
+    else:
+      denom = self.ms + self.eps
     self.mom = self.mom * self.mu + (g * self.lr) / np.sqrt(denom)
     var -= self.mom
     return var
