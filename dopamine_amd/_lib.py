@@ -9,7 +9,7 @@ import os
 from dopamine_amd import _build
 from dopamine_amd._build import HEADER, LIB_PATH  # noqa: F401
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 OK = 0
 (ST_OK, ST_EMPTY_TREE, ST_MAX_ATTEMPTS, ST_TAPE_EXHAUSTED, ST_NEG_PRIORITY, ST_TOO_FEW, ST_BAD_INDEX,
  ST_BROADCAST) = range(8)
@@ -71,6 +71,21 @@ class CnnParams(ctypes.Structure):
 
 class CnnActs(ctypes.Structure):
   _fields_ = [(n, ctypes.c_void_p) for n in ('a1', 'a2', 'a3', 'h', 'out')]
+
+
+MLP_MAX_IN, MLP_MAX_LAYERS, MLP_MAX_WIDTH = 16, 4, 1024    # DQ_MLP_MAX_*
+
+
+class MlpParams(ctypes.Structure):
+  """dq_mlp_params: the classic-control MLP over a flat parameter (or gradient) buffer."""
+  _fields_ = [('in_dim', ctypes.c_int32), ('n_layers', ctypes.c_int32),
+              ('width', ctypes.c_int32 * 4), ('n_out', ctypes.c_int32), ('pad_', ctypes.c_int32),
+              ('w', ctypes.c_void_p * 5), ('b', ctypes.c_void_p * 5),
+              ('in_min', ctypes.c_float * 16), ('in_range', ctypes.c_float * 16)]
+
+
+class MlpActs(ctypes.Structure):
+  _fields_ = [('x0', ctypes.c_void_p), ('h', ctypes.c_void_p * 4), ('out', ctypes.c_void_p)]
 
 
 class C51Target(ctypes.Structure):
@@ -213,6 +228,13 @@ SIGNATURES = {
     'dq_cnn_backward_torso_opt': [ctypes.POINTER(CnnParams), ctypes.POINTER(CnnParams), _I32, _P,
                                   ctypes.POINTER(CnnActs), ctypes.POINTER(CnnActs), _P,
                                   ctypes.POINTER(AdamArgs), _P, _P, _P],
+    'dq_mlp_workspace_floats': [_I32, ctypes.POINTER(MlpParams)],
+    'dq_mlp_forward': [ctypes.POINTER(MlpParams), _I32, _P, _I32, ctypes.POINTER(MlpActs), _P, _P],
+    'dq_mlp_backward': [ctypes.POINTER(MlpParams), ctypes.POINTER(MlpParams), _I32,
+                        ctypes.POINTER(MlpActs), _P, ctypes.POINTER(MlpActs), _P, _P],
+    'dq_mlp_backward_layer': [ctypes.POINTER(MlpParams), ctypes.POINTER(MlpParams), _I32,
+                              ctypes.POINTER(MlpActs), _P, ctypes.POINTER(MlpActs), _P, _I32, _I32,
+                              _P],
     'dq_iqn_head_forward': [ctypes.POINTER(IqnHead), _I32, _I32, _P, _P, ctypes.POINTER(IqnActs),
                             _P, _P],
     'dq_iqn_head_backward': [ctypes.POINTER(IqnHead), ctypes.POINTER(IqnHead), _I32, _I32, _P,
@@ -244,6 +266,7 @@ SIGNATURES = {
 }
 RESTYPES = {'dq_last_error': ctypes.c_char_p, 'dq_build_flags': ctypes.c_char_p, 'dq_cnn_workspace_floats': ctypes.c_size_t,
             'dq_iqn_workspace_floats': ctypes.c_size_t,
+            'dq_mlp_workspace_floats': ctypes.c_size_t,
             'dq_cnn_fc2_parts_offset': ctypes.c_size_t}
 
 

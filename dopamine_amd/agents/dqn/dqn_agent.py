@@ -85,6 +85,7 @@ class DQNAgent(object):
                use_hip_graph=True,
                pipeline=True,
                use_hip_cnn=True,
+               use_hip_mlp=None,
                fuse_optimizer=True,
                pair_forward=False,
                ride_replay=True,
@@ -146,6 +147,10 @@ class DQNAgent(object):
     self.use_hip_graph = use_hip_graph
     self.pipeline = pipeline
     self.use_hip_cnn = use_hip_cnn
+    # the classic-control MLPs on the HIP executor (dopamine_amd/mlp.py): None -- on for the
+    # gym networks but CartpoleDQNNetwork (config 1 keeps its PyTorch path); True / False
+    # -- on for every gym network / PyTorch everywhere.  Single replica only.
+    self.use_hip_mlp = use_hip_mlp
     self.fuse_optimizer = fuse_optimizer
     self.pair_forward = pair_forward
     self.ride_replay = ride_replay
@@ -314,6 +319,9 @@ class DQNAgent(object):
       d['target_out'] = self._hip['target'][c].acts['out']
       for k in ('a1', 'a2', 'a3', 'h'):    # the online forward's ReLU outputs (mask pinning)
         d['act_' + k] = self._hip['online'].acts[k]
+    elif self._mlp is not None:
+      d['online_out'] = self._mlp['online'].acts['out']
+      d['target_out'] = self._mlp['target'][c].acts['out']
     elif getattr(self, '_last_online_out', None) is not None and 'q' in (self._ptgt[c] or {}):
       d['online_out'] = self._last_online_out       # the PyTorch-network path (e.g. CartPole)
       d['target_out'] = self._ptgt[c]['q']
@@ -337,13 +345,33 @@ class DQNAgent(object):
         batch_size=self._batch_size, device=self._device)
 
   def _make_network(self, seed):
-    if self.network is networks.CartpoleDQNNetwork:
+    if self._is_gym_network():
       return self.network(self.num_actions, device=self._device, seed=seed)
     return self.network(self.num_actions, stack_size=self.stack_size, device=self._device, seed=seed)
+
+  def _is_gym_network(self):
+    return (isinstance(self.network, type) and
+            issubclass(self.network, networks.BasicDiscreteDomainNetwork))
+
+  def _build_mlp(self):
+    """The HIP MLP executors (one online, one per pipeline slot for the target), or None."""
+    on = self.use_hip_mlp
+    if on is None:
+      on = self._is_gym_network() and self.network is not networks.CartpoleDQNNetwork
+    if not on or self._pg is not None:
+      return None
+    if not self._is_gym_network():
+      raise ValueError('use_hip_mlp=True needs a classic-control network (gym_lib), got %r'
+                       % (self.network,))
+    from dopamine_amd.mlp import HipMLP
+    B = self._batch_size
+    return dict(online=HipMLP(self.online_convnet, B),
+                target=[HipMLP(self.target_convnet, B) for _ in range(2)])
 
   def _build_networks(self):
     self.online_convnet = self._make_network(self._seed)
     self.target_convnet = self._make_network(self._seed + 1)
+    self._mlp = self._build_mlp()
     # Nature-CNN nets run on the HIP implicit-GEMM kernels (dopamine_amd/cnn.py);
     # the torch modules keep the parameters (flat buffer) and serve action selection.
     self._hip = None
@@ -361,12 +389,16 @@ class DQNAgent(object):
       if ready is not None:             # already computed by _forward_pair
         return ready
       return self._hip['online'].forward(x)
+    if self._mlp is not None:
+      return self._mlp['online'].forward(x)
     return self.online_convnet(self._state_input(x))
 
   def _target_net(self, x, slot):
     """Target network output (no gradient) into pipeline slot ``slot``."""
     if self._hip is not None:
       return self._hip['target'][slot].forward(x)
+    if self._mlp is not None:
+      return self._mlp['target'][slot].forward(x)
     with torch.no_grad():
       return self.target_convnet(self._state_input(x))
 
@@ -426,6 +458,9 @@ class DQNAgent(object):
       else:
         self._hip['online'].backward(g, groups=groups)
       return
+    if self._mlp is not None:       # likewise, by the MLP executor's L + 1 launches
+      self._mlp['online'].backward(g)
+      return
     # Fresh per-parameter gradients (no flat-buffer zeroing + accumulate kernels);
     # the multi-tensor TF1 Adam reads them in place.
     for prm in self.online_convnet.parameters():
@@ -435,7 +470,7 @@ class DQNAgent(object):
       self.online_convnet.fp.gather_grads()
 
   def _needs_flat_grad(self):
-    return (self._hip is not None or self._pg is not None or
+    return (self._hip is not None or self._mlp is not None or self._pg is not None or
             not getattr(self._opt, 'supports_multi', False))
 
   # Pipelined step.  Slot c holds step t's batch and its target-net outputs.
@@ -643,7 +678,7 @@ class DQNAgent(object):
     if self._pairs():               # the target forward runs with the online one (_forward_pair)
       return
     tg = self._target_forward(t, i)
-    if self._hip is not None:       # persistent per-slot output buffers: no copy
+    if self._hip is not None or self._mlp is not None:   # persistent per-slot output buffers: no copy
       self._ptgt[i] = tg
       return
     if self._ptgt[i] is None:
@@ -1211,6 +1246,8 @@ class DQNAgent(object):
   def _q_values(self, state_np):
     if self._hip is not None and self.use_hip_graph:
       return self._act_q(state_np)
+    if self._mlp is not None:
+      return self._act_q_mlp(state_np)
     # (1, *observation_shape, stack) -> (1, stack, *observation_shape): the layout the
     # replay's gather hands the network in training (float32 / 255 for uint8 frames,
     # the observation dtype otherwise; the network casts, as the reference's do)
@@ -1252,6 +1289,39 @@ class DQNAgent(object):
     scale = 1.0 / 255.0 if np.dtype(self.observation_dtype) == np.uint8 else 1.0
     np.multiply(state_np, scale, out=pin.numpy(), casting='unsafe')
     x.copy_(pin, non_blocking=True)
+    g.replay()
+    return q
+
+  def _act_q_mlp(self, state_np):
+    """Q-values for action selection on the HIP MLP at batch 1, the analogue of _act_q: the
+    three launches and the Q reduction are one captured graph (use_hip_graph), the state
+    goes up through a pinned staging buffer in the observation's own dtype and is cast to
+    float32 in the first kernel.  (stack_size 1: the flattened state is the observation.)"""
+    if self._act is None:
+      from dopamine_amd.mlp import HipMLP
+      exe = HipMLP(self.online_convnet, 1)
+      dt = torch.float32 if np.dtype(self.observation_dtype) == np.float32 else torch.float64
+      x = torch.zeros(exe.D, dtype=dt, device=self._device)
+      pin = torch.empty(exe.D, dtype=dt).pin_memory()
+      g = None
+      if self.use_hip_graph:
+        main = torch.cuda.current_stream(self._device)
+        warm = torch.cuda.Stream(self._device)
+        warm.wait_stream(main)
+        with torch.cuda.stream(warm):
+          self._q_from_output(exe.forward(x))
+        main.wait_stream(warm)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+          q = self._q_from_output(exe.forward(x))
+        self._act = (exe, x, pin, g, q)
+      else:
+        self._act = (exe, x, pin, None, None)
+    exe, x, pin, g, q = self._act
+    pin.numpy()[:] = np.asarray(state_np).reshape(-1)
+    x.copy_(pin, non_blocking=True)
+    if g is None:
+      return self._q_from_output(exe.forward(x))
     g.replay()
     return q
 

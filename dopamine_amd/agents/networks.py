@@ -206,28 +206,88 @@ class ImplicitQuantileNetwork(_Net):
     return F.linear(h, self.fp['fc2_w'], self.fp['fc2_b']), taus
 
 
-class CartpoleDQNNetwork(_Net):
-  """gym_lib.py:75-132: rescale to [-1, 1] then FC 512-512-A."""
+class BasicDiscreteDomainNetwork(_Net):
+  """gym_lib.py:75-110 (_basic_discrete_domain_network): the observation rescaled to
+  [-1, 1] by the domain's MIN / MAX, fully connected ReLU layers of ``network_size``, a
+  linear layer of num_actions (Q-values) or num_actions * num_atoms (C51 logits) outputs.
+  Xavier-uniform weights, zero biases (slim's defaults).  ``forward`` is the PyTorch path
+  (``use_hip_mlp=False``); dopamine_amd.mlp.HipMLP runs the same parameters on the HIP
+  kernels."""
 
-  MIN = np.array([-2.4, -5., -math.pi / 12., -math.pi * 2.])
-  MAX = np.array([2.4, 5., math.pi / 12., math.pi * 2.])
+  MIN = MAX = None      # the domain's observation bounds (float64), set by subclasses
 
-  def __init__(self, num_actions, device='cuda', seed=0, network_size=(512, 512)):
-    self.A, self.sizes = num_actions, tuple(network_size)
+  def __init__(self, num_actions, num_atoms=None, stack_size=1, device='cuda', seed=0,
+               network_size=(512, 512)):
+    self.A, self.N, self.sizes = num_actions, num_atoms, tuple(network_size)
+    self.D = int(len(self.MIN)) * int(stack_size)
+    assert stack_size == 1, 'the classic-control domains stack one observation'
     super().__init__(device, seed, init='xavier')
     self._min = torch.tensor(self.MIN, dtype=torch.float32, device=device)
     self._rng = torch.tensor(self.MAX - self.MIN, dtype=torch.float32, device=device)
 
+  @property
+  def n_out(self):
+    return self.A * (self.N or 1)
+
   def shapes(self):
-    dims = [4] + list(self.sizes)
+    dims = [self.D] + list(self.sizes)
     s = []
     for i in range(len(self.sizes)):
       s += [('fc%d_w' % i, (dims[i + 1], dims[i])), ('fc%d_b' % i, (dims[i + 1],))]
-    return s + [('out_w', (self.A, dims[-1])), ('out_b', (self.A,))]
+    return s + [('out_w', (self.n_out, dims[-1])), ('out_b', (self.n_out,))]
 
   def forward(self, x):
     h = x.reshape(x.shape[0], -1).float()
     h = 2.0 * ((h - self._min) / self._rng) - 1.0
     for i in range(len(self.sizes)):
       h = F.relu(F.linear(h, self.fp['fc%d_w' % i], self.fp['fc%d_b' % i]))
-    return F.linear(h, self.fp['out_w'], self.fp['out_b'])
+    out = F.linear(h, self.fp['out_w'], self.fp['out_b'])
+    return out if self.N is None else out.view(-1, self.A, self.N)
+
+
+_CARTPOLE_MIN = np.array([-2.4, -5., -math.pi / 12., -math.pi * 2.])
+_CARTPOLE_MAX = np.array([2.4, 5., math.pi / 12., math.pi * 2.])
+_ACROBOT_MIN = np.array([-1., -1., -1., -1., -5., -5.])
+_ACROBOT_MAX = np.array([1., 1., 1., 1., 5., 5.])
+
+
+class CartpoleDQNNetwork(BasicDiscreteDomainNetwork):
+  """gym_lib.py:113-132: rescale to [-1, 1] then FC 512-512-A."""
+
+  MIN, MAX = _CARTPOLE_MIN, _CARTPOLE_MAX
+
+  def __init__(self, num_actions, device='cuda', seed=0, network_size=(512, 512), num_atoms=None,
+               stack_size=1):
+    assert num_atoms is None
+    super().__init__(num_actions, None, stack_size, device, seed, network_size)
+
+
+class CartpoleRainbowNetwork(BasicDiscreteDomainNetwork):
+  """gym_lib.py:227-252 -> logits (B, A, N)."""
+
+  MIN, MAX = _CARTPOLE_MIN, _CARTPOLE_MAX
+
+  def __init__(self, num_actions, num_atoms=51, stack_size=1, device='cuda', seed=0,
+               network_size=(512, 512)):
+    super().__init__(num_actions, num_atoms, stack_size, device, seed, network_size)
+
+
+class AcrobotDQNNetwork(BasicDiscreteDomainNetwork):
+  """gym_lib.py:255-273: rescale to [-1, 1] then FC 512-512-A."""
+
+  MIN, MAX = _ACROBOT_MIN, _ACROBOT_MAX
+
+  def __init__(self, num_actions, device='cuda', seed=0, network_size=(512, 512), num_atoms=None,
+               stack_size=1):
+    assert num_atoms is None
+    super().__init__(num_actions, None, stack_size, device, seed, network_size)
+
+
+class AcrobotRainbowNetwork(BasicDiscreteDomainNetwork):
+  """gym_lib.py:295-317 -> logits (B, A, N)."""
+
+  MIN, MAX = _ACROBOT_MIN, _ACROBOT_MAX
+
+  def __init__(self, num_actions, num_atoms=51, stack_size=1, device='cuda', seed=0,
+               network_size=(512, 512)):
+    super().__init__(num_actions, num_atoms, stack_size, device, seed, network_size)

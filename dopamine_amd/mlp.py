@@ -1,0 +1,96 @@
+"""HIP executor of the classic-control MLPs over a network's flat parameter buffer.
+
+Forward and backward of ``networks.BasicDiscreteDomainNetwork`` (gym_lib.py:75-110: the
+rescale to [-1, 1], L ReLU layers, a linear output layer) run as L + 1 and L + 1 launches
+on the exact-fp32 matrix cores (dopamine_amd/csrc/mlp.hip) instead of ~15 library launches
+and autograd.  The first launch takes the state as the replay hands it over (float64 for
+the gym configs) and casts it in the kernel; the backward writes every weight / bias
+gradient straight into the flat gradient buffer (plain stores), which the TF1 optimizer
+kernel then consumes.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from dopamine_amd import _lib
+
+
+def _params_struct(net, buf):
+  fp = net.fp
+  L = len(net.sizes)
+  s = _lib.MlpParams(in_dim=int(net.D), n_layers=L, n_out=int(net.n_out))
+  base = buf.data_ptr()
+  names = ['fc%d' % i for i in range(L)] + ['out']
+  for i, n in enumerate(names):
+    s.w[i] = base + 4 * fp.offsets[n + '_w'][0]
+    s.b[i] = base + 4 * fp.offsets[n + '_b'][0]
+  for i, w in enumerate(net.sizes):
+    s.width[i] = int(w)
+  lo = np.asarray(net.MIN, dtype=np.float64)
+  rng = (np.asarray(net.MAX, dtype=np.float64) - lo).astype(np.float32)   # subtracted in float64
+  for d in range(int(net.D)):
+    s.in_min[d] = float(np.float32(lo[d]))
+    s.in_range[d] = float(rng[d])
+  return s
+
+
+class HipMLP(object):
+  """Executes a ``BasicDiscreteDomainNetwork``'s parameters (read in place) with the HIP
+  kernels.  ``forward`` keeps its activations for ``backward``; use one executor per
+  concurrent stream (online vs target)."""
+
+  def __init__(self, net, batch_size):
+    L = len(net.sizes)
+    if not (1 <= L <= _lib.MLP_MAX_LAYERS and 1 <= net.D <= _lib.MLP_MAX_IN and
+            all(1 <= w <= _lib.MLP_MAX_WIDTH for w in net.sizes) and
+            1 <= net.n_out <= _lib.MLP_MAX_WIDTH):
+      raise ValueError('HipMLP: unsupported geometry D=%d sizes=%r n_out=%d (D <= 16, 1..4 layers '
+                       'of width <= 1024, n_out <= 1024)' % (net.D, net.sizes, net.n_out))
+    self.net = net
+    self.B = B = int(batch_size)
+    self.D, self.n_out = int(net.D), int(net.n_out)
+    dev = net.fp.flat.device
+    mk = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
+    self.acts = dict(x0=mk(B, self.D), out=mk(B, self.n_out))
+    self.dacts = {}
+    for i, w in enumerate(net.sizes):
+      self.acts['h%d' % i] = mk(B, w)
+      self.dacts['h%d' % i] = mk(B, w)
+    self._p = _params_struct(net, net.fp.flat)
+    self._g = _params_struct(net, net.fp.grad)
+    self.ws = mk(int(_lib.lib.dq_mlp_workspace_floats(B, ctypes.byref(self._p))) + 64)
+    self._a = self._acts_struct(self.acts)
+    self._d = self._acts_struct(self.dacts)
+
+  @staticmethod
+  def _acts_struct(t):
+    s = _lib.MlpActs(x0=t['x0'].data_ptr() if 'x0' in t else None,
+                     out=t['out'].data_ptr() if 'out' in t else None)
+    for i in range(4):
+      if 'h%d' % i in t:
+        s.h[i] = t['h%d' % i].data_ptr()
+    return s
+
+  def forward(self, x):
+    """x: the states, B * D contiguous float64 or float32 values (any shape, e.g. the
+    gather's (B, 1, D, 1)).  Returns the (B, n_out) output buffer (overwritten by the next
+    call)."""
+    assert x.numel() == self.B * self.D and x.is_contiguous(), (tuple(x.shape), self.B, self.D)
+    assert x.dtype in (torch.float64, torch.float32), x.dtype
+    _lib.check(_lib.lib.dq_mlp_forward(ctypes.byref(self._p), self.B, x.data_ptr(),
+                                       int(x.dtype == torch.float64), ctypes.byref(self._a),
+                                       self.ws.data_ptr(), _lib.stream_of(x.device)),
+               'dq_mlp_forward')
+    return self.acts['out']
+
+  def backward(self, dout):
+    """dout: (B, n_out) = d loss / d output of the last ``forward``.  Writes all parameter
+    gradients into net.fp.grad."""
+    assert dout.numel() == self.B * self.n_out and dout.is_contiguous()
+    assert dout.dtype == torch.float32
+    _lib.check(_lib.lib.dq_mlp_backward(ctypes.byref(self._p), ctypes.byref(self._g), self.B,
+                                        ctypes.byref(self._a), dout.data_ptr(),
+                                        ctypes.byref(self._d), self.ws.data_ptr(),
+                                        _lib.stream_of(dout.device)), 'dq_mlp_backward')
+    return self.net.fp.grad

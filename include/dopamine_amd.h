@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define DQ_ABI_VERSION 9
+#define DQ_ABI_VERSION 10
 
 /* host-side return codes */
 #define DQ_OK 0
@@ -521,6 +521,52 @@ int dq_cnn_backward_torso_opt(const dq_cnn_params* p, const dq_cnn_params* g, in
                               const float* x, const dq_cnn_acts* a, dq_cnn_acts* d, float* ws,
                               const dq_adam_args* opt, float* head_begin, float* head_end,
                               void* stream);
+
+/* ---------------- classic-control MLP (gym_lib.py:75-110) on fp32 MFMA ----------------
+ * _basic_discrete_domain_network: the observation rescaled to [-1, 1], L hidden layers
+ * ReLU(W x + b), a linear output layer.  Weights (out, in) row-major, views into the flat
+ * parameter buffer.  Layer l = 0..L-1 is hidden layer l, layer L the output layer.
+ * Supported: 1 <= in_dim <= 16, 1 <= n_layers <= 4, 1 <= width, n_out <= 1024, batch >= 1
+ * (checked on the host); ragged edges are handled in the kernels. */
+#define DQ_MLP_MAX_IN 16
+#define DQ_MLP_MAX_LAYERS 4
+#define DQ_MLP_MAX_WIDTH 1024
+typedef struct dq_mlp_params {
+  int32_t in_dim;                 /* D: observation floats (gym_lib.py:91) */
+  int32_t n_layers;               /* L: hidden layers (gym_lib.py:93-97) */
+  int32_t width[4];               /* their widths (network_size) */
+  int32_t n_out;                  /* num_actions, or num_actions * num_atoms (gym_lib.py:98-103) */
+  int32_t pad_;
+  float* w[5]; float* b[5];       /* w[l] (width[l], in), b[l]; w[L] (n_out, width[L-1]), b[L] */
+  float in_min[16];               /* float32(min_vals)             (gym_lib.py:104-108) */
+  float in_range[16];             /* float32(max_vals - min_vals), subtracted in float64 */
+} dq_mlp_params;
+typedef struct dq_mlp_acts {      /* per-call activations (or their gradients) */
+  float* x0;                      /* (B, D) the rescaled input (no gradient is formed for it) */
+  float* h[4];                    /* (B, width[l]) post-ReLU; as gradients: d loss / d pre-activation */
+  float* out;                     /* (B, n_out) (as a gradient: unused, dout is passed itself) */
+} dq_mlp_acts;
+/* floats of workspace the calls below need for this batch and network (may be 0) */
+size_t dq_mlp_workspace_floats(int32_t batch, const dq_mlp_params* p);
+/* forward (gym_lib.py:104-110): x (B, D) as the replay hands it over, float64 (x_is_f64) or
+   float32.  The first launch casts to float32, rescales -- t = x - in_min; t = t / in_range
+   (correctly rounded); x0 = 2 t - 1, uncontracted -- and runs layer 0; L more launches
+   follow, one per layer. */
+int dq_mlp_forward(const dq_mlp_params* p, int32_t batch, const void* x, int32_t x_is_f64,
+                   dq_mlp_acts* a, float* ws, void* stream);
+/* backward from dout (B, n_out): EVERY weight / bias gradient into g (plain stores; no
+   accumulation, no memset, no float atomics: bitwise reproducible); d->h[l] receive the
+   hidden layers' pre-activation gradients.  L + 1 launches: layer l's weight + bias
+   gradient and its input gradient are groups of one launch (l = L..1), layer 0's weight +
+   bias gradient the last. */
+int dq_mlp_backward(const dq_mlp_params* p, const dq_mlp_params* g, int32_t batch,
+                    const dq_mlp_acts* a, const float* dout, dq_mlp_acts* d, float* ws,
+                    void* stream);
+/* one layer of the backward alone: part 1 = weight and bias gradient, part 0 = input
+   gradient into d->h[layer - 1] (not for layer 0).  Bitwise what dq_mlp_backward computes. */
+int dq_mlp_backward_layer(const dq_mlp_params* p, const dq_mlp_params* g, int32_t batch,
+                          const dq_mlp_acts* a, const float* dout, dq_mlp_acts* d, float* ws,
+                          int32_t layer, int32_t part, void* stream);
 
 /* ImplicitQuantileNetwork's quantile head (atari_lib.py:147-199) on the fp32 matrix cores.
    R = nq * batch rows ordered q * batch + b (tf.tile, atari_lib.py:174). */

@@ -1,0 +1,150 @@
+"""A/B of the classic-control agents' two network paths on one device: the HIP MLP executor
+(use_hip_mlp=True) against PyTorch's library GEMMs + autograd (use_hip_mlp=False), with an
+A/A pair (a second HIP agent) for the noise floor.
+
+For each of rainbow_cartpole.gin and dqn_cartpole.gin (where the False arm is config 1's
+default path) the agents are built from the same seed over the same 3,000-transition
+buffer, their graphs are primed, and they alternate, the order reversed every round, over
+``--rounds`` rounds of two timed loops, the profiler off and a device synchronise closing
+each window:
+  learner  gradient steps/s of ``train_gradient_steps`` in windows of at least 0.3 s;
+  agent    environment steps/s of ``begin_episode`` / ``step`` against the environment,
+           a gradient step every update_period = 4 steps and the batch-1 acting forward
+           every step.
+Prints every round, then per loop the medians, the spread (max - min) of each arm, the
+smallest HIP / PyTorch pair ratio and the A/A difference.
+    python tools/gym_mlp_ab.py [--rounds 7] [--configs rainbow_cartpole dqn_cartpole]
+--profile-arm runs 300 learner steps and 300 agent steps of the HIP arm only (the run to put
+under a kernel-trace profiler for the per-launch table)."""
+import argparse
+import os
+import random
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from dopamine_amd import gin_lite  # noqa: E402
+from dopamine_amd.discrete_domains import gym_lib, run_experiment  # noqa: E402
+
+_AGENTS = os.path.join(ROOT, 'dopamine_amd', 'agents')
+CONFIGS = {'rainbow_cartpole': (os.path.join(_AGENTS, 'rainbow', 'configs', 'rainbow_cartpole.gin'),
+                                'RainbowAgent'),
+           'dqn_cartpole': (os.path.join(_AGENTS, 'dqn', 'configs', 'dqn_cartpole.gin'), 'DQNAgent')}
+
+
+def build(config, hip):
+  gin, cls = CONFIGS[config]
+  gin_lite.clear_config()
+  run_experiment.load_gin_configs([gin], ['%s.use_hip_mlp = %s' % (cls, bool(hip))])
+  env = gym_lib.create_gym_environment()
+  env.environment.seed(0)
+  np.random.seed(0)
+  random.seed(0)
+  agent = run_experiment.create_agent(None, env)
+  gin_lite.clear_config()
+  assert (agent._mlp is not None) == bool(hip)
+  rs = np.random.RandomState(1)
+  obs = env.reset()
+  for _ in range(3000):
+    a = int(rs.randint(agent.num_actions))
+    nobs, r, done, _ = env.step(a)
+    agent._store_transition(np.asarray(obs).reshape(-1, 1), a, r, done)
+    obs = env.reset() if done else nobs
+  while not agent.graphs_primed():
+    agent.train_gradient_steps(5)
+  run_agent_loop(agent, env, 64)            # the interleaved graphs and the acting graph too
+  torch.cuda.synchronize()
+  return agent, env
+
+
+def run_learner(agent, n):
+  torch.cuda.synchronize()
+  t0 = time.perf_counter()
+  agent.train_gradient_steps(n)
+  torch.cuda.synchronize()
+  return n / (time.perf_counter() - t0)
+
+
+def run_agent_loop(agent, env, n):
+  """n environment steps as the Runner drives them (episodes capped at 200 steps)."""
+  torch.cuda.synchronize()
+  t0 = time.perf_counter()
+  done, length, action = True, 0, 0
+  for _ in range(n):
+    if done or length >= 200:
+      if not done:
+        agent.end_episode(1.0)
+      action, length = agent.begin_episode(env.reset()), 0
+    obs, r, done, _ = env.step(action)
+    length += 1
+    if done:
+      agent.end_episode(r)
+    else:
+      action = agent.step(r, obs)
+  torch.cuda.synchronize()
+  return n / (time.perf_counter() - t0)
+
+
+def summarize(name, rows):
+  """rows: per round {arm: rate}."""
+  arms = list(rows[0])
+  med = {a: statistics.median(r[a] for r in rows) for a in arms}
+  for a in arms:
+    v = [r[a] for r in rows]
+    print('%s [%s] median %.1f /s  min %.1f  max %.1f  spread %.2f%%' % (
+        name, a, med[a], min(v), max(v), 100 * (max(v) - min(v)) / med[a]), flush=True)
+  pairs = [r['hip'] / r['torch'] for r in rows]
+  aa = [r['hip'] / r['hip2'] for r in rows]
+  print('%s hip/torch: median of medians %.4f  smallest pair %.4f  largest pair %.4f' % (
+      name, med['hip'] / med['torch'], min(pairs), max(pairs)), flush=True)
+  print('%s A/A hip/hip2: median of medians %.4f  pairs %.4f .. %.4f' % (
+      name, med['hip'] / med['hip2'], min(aa), max(aa)), flush=True)
+
+
+def main():
+  ap = argparse.ArgumentParser()
+  ap.add_argument('--rounds', type=int, default=7)
+  ap.add_argument('--configs', nargs='*', default=list(CONFIGS))
+  ap.add_argument('--window', type=float, default=0.3, help='seconds per learner window, at least')
+  ap.add_argument('--agent-steps', type=int, default=2000)
+  ap.add_argument('--profile-arm', action='store_true')
+  args = ap.parse_args()
+  torch.cuda.set_device(0)
+  if args.profile_arm:
+    agent, env = build(args.configs[0], True)
+    print('profile arm: %.1f gradient steps/s, %.1f env steps/s' % (
+        run_learner(agent, 300), run_agent_loop(agent, env, 300)), flush=True)
+    return
+  for config in args.configs:
+    arms = {'hip': build(config, True), 'torch': build(config, False), 'hip2': build(config, True)}
+    # learner windows of at least --window seconds on the slowest arm
+    n = 200
+    slowest = min(run_learner(a, n) for a, _ in arms.values())
+    n = max(n, int(slowest * args.window * 1.25))
+    print('# %s: learner windows of %d gradient steps, agent windows of %d env steps' % (
+        config, n, args.agent_steps), flush=True)
+    rows = {'learner': [], 'agent': []}
+    for rnd in range(args.rounds):
+      order = list(arms) if rnd % 2 == 0 else list(arms)[::-1]
+      for loop in ('learner', 'agent'):
+        row = {}
+        for a in order:
+          agent, env = arms[a]
+          row[a] = run_learner(agent, n) if loop == 'learner' else run_agent_loop(
+              agent, env, args.agent_steps)
+          print('%s round %d %s [%s] %.1f /s' % (config, rnd, loop, a, row[a]), flush=True)
+        rows[loop].append(row)
+    for loop in ('learner', 'agent'):
+      summarize('%s %s' % (config, loop), rows[loop])
+    for agent, _ in arms.values():
+      agent.close()
+
+
+if __name__ == '__main__':
+  main()
