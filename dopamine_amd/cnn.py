@@ -120,23 +120,33 @@ class HipNatureCNN(object):
     others' slices gathered in launch 5 (defer_ag: gathered by the next step's
     ``forward_fused*(..., peer=)`` or ``PeerExchange.all_gather`` instead), the conv bucket
     in launch 6.  Rider i rides in launch 1 + i."""
-    dout = dout.reshape(self.B, self.n_out)
-    assert dout.is_contiguous() and self._x is not None
+    dout, common = self._backward_args(dout)
     args = self._adam_args(adam, slot)
     args.no_grad_store = 0
+    arr, n, hn = self._riders_and_head(riders, head)
+    _lib.check(_lib.lib.dq_cnn_backward_peer(
+        *common, arr, n, ctypes.byref(args), hn, ctypes.byref(peer), int(bool(defer_ag)),
+        self._stream(dout)), 'dq_cnn_backward_peer')
+    return self.net.fp.grad
+
+  def _backward_args(self, dout):
+    """dout as (B, n_out), and the arguments every backward entry point starts with:
+    parameters, gradients, batch, input, activations, dout, activation gradients, workspace."""
+    dout = dout.reshape(self.B, self.n_out)
+    assert dout.is_contiguous() and self._x is not None
+    return dout, (ctypes.byref(self._p), ctypes.byref(self._g), self.B, self._x.data_ptr(),
+                  ctypes.byref(self._a), dout.data_ptr(), ctypes.byref(self._d),
+                  self.ws.data_ptr())
+
+  def _riders_and_head(self, riders, head):
+    """(dq_rider array, its length, dq_cnn_net of ``head`` = (executor, x) or None)."""
     riders = riders or []
     arr = (_lib.Rider * max(1, len(riders)))(*riders)
     hn = None
     if head is not None:
       assert head[0] is not self
       hn = ctypes.byref(head[0].cnn_net(head[1]))
-    _lib.check(_lib.lib.dq_cnn_backward_peer(
-        ctypes.byref(self._p), ctypes.byref(self._g), self.B, self._x.data_ptr(),
-        ctypes.byref(self._a), dout.data_ptr(), ctypes.byref(self._d), self.ws.data_ptr(),
-        arr, len(riders), ctypes.byref(args), hn, ctypes.byref(peer), int(bool(defer_ag)),
-        self._stream(dout)),
-        'dq_cnn_backward_peer')
-    return self.net.fp.grad
+    return arr, len(riders), hn
 
   def backward(self, dout, parallel=False, adam=None, slot=0, groups=None, riders=None, head=None,
                head_from=3):
@@ -169,42 +179,26 @@ class HipNatureCNN(object):
     95.9 us per backward, tools/bench_hipcnn.py): the cross-queue edges cost
     more than the overlap buys, and the 135-147 KB-LDS blocks cannot share a CU
     with the other stream's.  Kept for experimentation; off by default."""
-    dout = dout.reshape(self.B, self.n_out)
-    assert dout.is_contiguous() and self._x is not None
+    dout, common = self._backward_args(dout)
     if riders or head is not None or (groups is not None and adam is not None):
       args = None if adam is None else ctypes.byref(self._adam_args(adam, slot))
-      riders = riders or []
-      arr = (_lib.Rider * max(1, len(riders)))(*riders)
-      hn = None
-      if head is not None:
-        assert head[0] is not self
-        hn = ctypes.byref(head[0].cnn_net(head[1]))
+      arr, n, hn = self._riders_and_head(riders, head)
       first, last = (0, 7) if groups is None else groups
       _lib.check(_lib.lib.dq_cnn_backward_riders(
-          ctypes.byref(self._p), ctypes.byref(self._g), self.B, self._x.data_ptr(),
-          ctypes.byref(self._a), dout.data_ptr(), ctypes.byref(self._d), self.ws.data_ptr(),
-          arr, len(riders), args, hn, int(head_from), int(first), int(last), self._stream(dout)),
+          *common, arr, n, args, hn, int(head_from), int(first), int(last), self._stream(dout)),
           'dq_cnn_backward_riders')
       return self.net.fp.grad
     if groups is not None:          # a sub-range of the 7 grouped launches
       _lib.check(_lib.lib.dq_cnn_backward_groups(
-          ctypes.byref(self._p), ctypes.byref(self._g), self.B, self._x.data_ptr(),
-          ctypes.byref(self._a), dout.data_ptr(), ctypes.byref(self._d), self.ws.data_ptr(),
-          int(groups[0]), int(groups[1]), self._stream(dout)), 'dq_cnn_backward_groups')
+          *common, int(groups[0]), int(groups[1]), self._stream(dout)), 'dq_cnn_backward_groups')
       return self.net.fp.grad
     if adam is not None:
       args = self._adam_args(adam, slot)
-      _lib.check(_lib.lib.dq_cnn_backward_adam(
-          ctypes.byref(self._p), ctypes.byref(self._g), self.B, self._x.data_ptr(),
-          ctypes.byref(self._a), dout.data_ptr(), ctypes.byref(self._d), self.ws.data_ptr(),
-          ctypes.byref(args), self._stream(dout)), 'dq_cnn_backward_adam')
+      _lib.check(_lib.lib.dq_cnn_backward_adam(*common, ctypes.byref(args), self._stream(dout)),
+                 'dq_cnn_backward_adam')
       return self.net.fp.grad
     if not parallel:
-      _lib.check(_lib.lib.dq_cnn_backward(ctypes.byref(self._p), ctypes.byref(self._g), self.B,
-                                          self._x.data_ptr(), ctypes.byref(self._a),
-                                          dout.data_ptr(), ctypes.byref(self._d),
-                                          self.ws.data_ptr(), self._stream(dout)),
-                 'dq_cnn_backward')
+      _lib.check(_lib.lib.dq_cnn_backward(*common, self._stream(dout)), 'dq_cnn_backward')
       return self.net.fp.grad
     main = torch.cuda.current_stream(dout.device)
     if self._dw_stream is None:
@@ -214,9 +208,8 @@ class HipNatureCNN(object):
 
     def layer(i, part, stream, ws):
       _lib.check(_lib.lib.dq_cnn_backward_layer(
-          ctypes.byref(self._p), ctypes.byref(self._g), self.B, self._x.data_ptr(),
-          ctypes.byref(self._a), dout.data_ptr(), ctypes.byref(self._d), ws.data_ptr(), i, part,
-          ctypes.c_void_p(stream.cuda_stream)), 'dq_cnn_backward_layer')
+          *common[:-1], ws.data_ptr(), i, part, ctypes.c_void_p(stream.cuda_stream)),
+          'dq_cnn_backward_layer')
 
     # ev[i] marks "input gradient of layer i-1 done" (ev[0]: dout ready)
     ev[0].record(main)

@@ -31,6 +31,9 @@
 #include "c51_dev.h"
 
 #include <cstring>
+#include <optional>
+#include <tuple>
+#include <type_traits>
 
 namespace dq {
 namespace cnn {
@@ -760,9 +763,22 @@ struct Fc1EpiOpt<2> {       // centered RMSProp (DQN, config 2)
   }
 };
 
+template <>
+struct Fc1EpiOpt<0> {       // no optimizer: the plain gradient store
+  static EpiGrad make(const dq_cnn_params*, const dq_cnn_params* g, const dq_adam_args*) {
+    return EpiGrad{g->fc1_w, g->fc1_b, kFlat};
+  }
+};
+
 // the same for fc2: fc2's weight gradient + optimizer in one vector epilogue
 template <int kOpt>
 struct Fc2EpiOpt;
+template <>
+struct Fc2EpiOpt<0> {
+  static EpiGrad make(const dq_cnn_params*, const dq_cnn_params* g, const dq_adam_args*) {
+    return EpiGrad{g->fc2_w, g->fc2_b, kHidden};
+  }
+};
 template <>
 struct Fc2EpiOpt<1> {
   static EpiGradAdamVec make(const dq_cnn_params* p, const dq_cnn_params* g, const dq_adam_args* o) {
@@ -933,6 +949,64 @@ void group_r(Ctx& c, const RiderDesc* r, Ops... ops) {
       group(c, RiderOp{*r}, ops...);
   else
     group(c, ops...);
+}
+
+// A launch list that names every op the launch can hold.  What is not there is dropped on the
+// host, before k_grouped is instantiated -- no pack ever carries a placeholder op:
+//   Absent         not there at compile time (the optimizer's part when kOpt == 0, a head
+//                  layer this kHeadFrom does not carry): the pack is simply shorter
+//   std::optional  there or not at run time (the head network's op, the peer gather): selects
+//                  between the pack with and the pack without it, as an if / else would
+//   std::tuple     its members, in order (the four sub-pixel tiles)
+// r: the launch's rider (group_r), or NoRider for a launch that never takes one (group).
+struct Absent {};
+struct NoRider {};
+template <bool kIs, class Op>
+auto when(Op op) {
+  if constexpr (kIs) return op;
+  else return Absent{};
+}
+template <class T>
+struct IsOptional : std::false_type {};
+template <class T>
+struct IsOptional<std::optional<T>> : std::true_type {};
+template <class T>
+struct IsTuple : std::false_type {};
+template <class... T>
+struct IsTuple<std::tuple<T...>> : std::true_type {};
+
+template <class R, class... Done>
+void launch_from(Ctx& c, R r, std::tuple<Done...> done) {
+  if constexpr (std::is_same_v<R, NoRider>)
+    std::apply([&](auto... o) { group(c, o...); }, done);
+  else
+    std::apply([&](auto... o) { group_r(c, r, o...); }, done);
+}
+template <class R, class... Done, class Op, class... Rest>
+void launch_from(Ctx& c, R r, std::tuple<Done...> done, Op op, Rest... rest) {
+  if constexpr (std::is_same_v<Op, Absent>) {
+    launch_from(c, r, done, rest...);
+  } else if constexpr (IsOptional<Op>::value) {
+    if (op)
+      launch_from(c, r, std::tuple_cat(done, std::make_tuple(*op)), rest...);
+    else
+      launch_from(c, r, done, rest...);
+  } else if constexpr (IsTuple<Op>::value) {
+    std::apply([&](auto... o) { launch_from(c, r, done, o..., rest...); }, op);
+  } else {
+    launch_from(c, r, std::tuple_cat(done, std::make_tuple(op)), rest...);
+  }
+}
+template <class R, class... Ops>
+void launch(Ctx& c, R r, Ops... ops) {
+  launch_from(c, r, std::tuple<>{}, ops...);
+}
+// the fused optimizer's range op over [w0, w1) of the flat buffer (OptPart), if there is one
+template <int kOpt>
+auto opt_part(const dq_cnn_params* p, const dq_cnn_params* g, const AdamHost& opt, float* w0,
+              float* w1) {
+  if constexpr (kOpt == 0) return Absent{};
+  else return OptPart<kOpt>::make(p, g, opt.a, w0, w1);
 }
 
 // Tile shapes: WM = WN = 1 with WK k-bands sized so K takes one or two slices
@@ -1217,6 +1291,117 @@ bool backward_layer(Ctx& c, const dq_cnn_params* p, const dq_cnn_params* g, int 
   }
 }
 
+// The backward's grouped ops for one network, each defined once for every schedule below
+// (the same tiles, split factors and slab order as backward_layer: bitwise identical
+// gradients).  Building one carves the three split-K slab regions out of the launch context's
+// workspace (ops of one launch never share one) -- in a dry run too, which is what sizes it.
+// kOpt (0 none, 1 TF1 Adam, 2 TF1 RMSProp) on an op: the optimizer in that op's epilogue.
+struct BwdOps {
+  const dq_cnn_params* p;
+  const dq_cnn_params* g;
+  const float* x;
+  const dq_cnn_acts* a;
+  const float* dout;      // null for the torso alone (no fc ops)
+  dq_cnn_acts* d;
+  int B, NO;
+  int K3, K1;             // the conv3 / conv2 and the conv1 weight gradients' K (pixels)
+  int ch3, nz3, ch1, nz1; // their split-K chunk and slab count
+  float* ws;
+  size_t o3, o2, o1;      // the conv3 / conv2 / conv1 slabs in ws
+  BwdOps(Ctx& c, const dq_cnn_params* p, const dq_cnn_params* g, int B, const float* x,
+         const dq_cnn_acts* a, const float* dout, dq_cnn_acts* d)
+      : p(p), g(g), x(x), a(a), dout(dout), d(d), B(B), NO(p->n_out), K3(B * 121), K1(B * 441) {
+    using W16 = Tile<1, 1, 16>;
+    ch3 = split_chunk(K3, kSplitConvW, W16::BKT), nz3 = (K3 + ch3 - 1) / ch3;
+    ch1 = split_chunk(K1, kSplitConv1W, W16::BKT), nz1 = (K1 + ch1 - 1) / ch1;
+    o3 = c.take((size_t)nz3 * 64 * (Conv3::K + 1));
+    o2 = c.take((size_t)nz3 * 64 * (Conv2::K + 1));
+    o1 = c.take((size_t)nz1 * 32 * (Conv1::K + 1));
+    ws = c.ws;
+  }
+  // fc2: dh = (dout W2) * (h > 0); dW2|db2 = dout^T [h | 1] (kOpt: dW_fc2a, Fc2EpiOpt)
+  auto dX_fc2() const {
+    return gemm_op<1, 1, 16>(RowKScalar{dout, NO}, ColK{p->fc2_w, kHidden},
+                             EpiMask{d->h, a->h, kHidden}, B, kHidden, NO, NO);
+  }
+  template <int kOpt = 0>
+  auto dW_fc2(const AdamHost& opt = AdamHost{nullptr}) const {
+    return gemm_op<4, 4, 1>(ColKScalar{dout, NO}, ColKOnes{a->h, kHidden},
+                            Fc2EpiOpt<kOpt>::make(p, g, opt.a), NO, kHidden + 1, B, B);
+  }
+  // fc1: da3 = (dh W1) * (a3 > 0); dW1|db1 = dh^T [a3 | 1] (kOpt: dW_fc1a, Fc1EpiOpt)
+  auto dX_fc1() const {
+    return gemm_op<1, 1, 16, kB1Late, kHidden, kFlat>(RowK{d->h, kHidden}, ColK{p->fc1_w, kFlat},
+                                                      EpiMask{d->a3, a->a3, kFlat}, B, kFlat,
+                                                      kHidden, kHidden);
+  }
+  template <int kOpt = 0>
+  auto dW_fc1(const AdamHost& opt = AdamHost{nullptr}) const {
+    return gemm_op<4, 4, 1>(ColK{d->h, kHidden}, ColKOnes{a->a3, kFlat},
+                            Fc1EpiOpt<kOpt>::make(p, g, opt.a), kHidden, kFlat + 1, B, B);
+  }
+  // conv3: da2 = col2im(da3, W3) * (a2 > 0); dW3|db3 = da3^T [im2col(a2) | 1] in nz3 slabs
+  auto dX_c3() const {
+    return gemm_op<1, 1, 16>(Col2im<Conv3>{d->a3}, WeightT<Conv3>{p->conv3_w},
+                             EpiMask{d->a2, a->a2, 64}, K3, 64, Conv3::K, Conv3::K);
+  }
+  auto dW_c3() const {
+    return gemm_op<1, 1, 16>(DyT<64>{d->a3}, Im2colT<Conv3>{a->a2},
+                             EpiPartial{ws + o3, 64, Conv3::K + 1}, 64, Conv3::K + 1, K3, ch3);
+  }
+  auto sum_c3() const {
+    return ReduceOp<EpiGrad>{ws + o3, nz3, 64, Conv3::K + 1,
+                             EpiGrad{g->conv3_w, g->conv3_b, Conv3::K}};
+  }
+  // conv2: da1 by sub-pixel class (subpix_op), as 8-wave tiles or -- two of them per 16-wave
+  // block of the grouped launch (+0.7%) -- as pairs; dW2|db2 = da2^T [im2col(a1) | 1] in nz3
+  // slabs, summed into EpiGrad or GradEpi<kOpt>
+  auto subpix() const {
+    return std::make_tuple(subpix_op<0, 0>(p, a, d, B), subpix_op<0, 1>(p, a, d, B),
+                           subpix_op<1, 0>(p, a, d, B), subpix_op<1, 1>(p, a, d, B));
+  }
+  auto subpix_pairs() const {
+    return std::apply([](auto... op) { return std::make_tuple(PairOp<decltype(op)>{op}...); },
+                      subpix());
+  }
+  auto dW_c2() const {
+    return gemm_op<1, 1, 16>(DyT<64>{d->a2}, Im2colT<Conv2>{a->a1},
+                             EpiPartial{ws + o2, 64, Conv2::K + 1}, 64, Conv2::K + 1, K3, ch3);
+  }
+  template <int kOpt = 0>
+  auto sum_c2(const AdamHost& opt = AdamHost{nullptr}) const {
+    using GE = GradEpi<kOpt>;
+    return ReduceOp<decltype(GE::make(0, 0, 0, 0, 0, opt, 0))>{
+        ws + o2, nz3, 64, Conv2::K + 1,
+        GE::make(g->conv2_w, g->conv2_b, Conv2::K, p->conv2_w, p->conv2_b, opt, 0)};
+  }
+  // conv1: dW1|db1 = da1^T [im2col(x) | 1] in nz1 slabs (no input gradient needed); its sum
+  // ends every schedule, so with kOpt its epilogue also advances the beta powers
+  auto dW_c1() const {
+    return gemm_op<1, 1, 16>(DyT<32>{d->a1}, Im2colT<Conv1>{x},
+                             EpiPartial{ws + o1, 32, Conv1::K + 1}, 32, Conv1::K + 1, K1, ch1);
+  }
+  template <int kOpt = 0>
+  auto sum_c1(const AdamHost& opt = AdamHost{nullptr}) const {
+    using GE = GradEpi<kOpt>;
+    return ReduceOp<decltype(GE::make(0, 0, 0, 0, 0, opt, 0))>{
+        ws + o1, nz1, 32, Conv1::K + 1,
+        GE::make(g->conv1_w, g->conv1_b, Conv1::K, p->conv1_w, p->conv1_b, opt, 1)};
+  }
+};
+
+// Layer L of a riding head network's forward (0..3: conv1, conv2, conv3, the fc1 slabs), there
+// if a head rides; L < 0: a launch before the schedule's first head layer
+template <int L>
+auto head_layer(const FwdOps* h) {
+  static_assert(L <= 3, "the head ends with its fc1 slabs");
+  if constexpr (L < 0) return Absent{};
+  else if constexpr (L == 0) return h ? std::optional(h->conv1()) : std::nullopt;
+  else if constexpr (L == 1) return h ? std::optional(h->conv2()) : std::nullopt;
+  else if constexpr (L == 2) return h ? std::optional(h->conv3<kB6Late>()) : std::nullopt;
+  else return h ? std::optional(h->fc1()) : std::nullopt;
+}
+
 // The torso's backward (conv3 .. conv1 from d a3, e.g. IQN's d state) in four grouped
 // launches of the full backward's tiles -- [dX conv3 | dW conv3 slabs] · [conv2's input
 // gradient by sub-pixel class | dW conv2 slabs | sum conv3] · [dW conv1 slabs | sum conv2] ·
@@ -1231,53 +1416,15 @@ void backward_torso_grouped(Ctx& c, const dq_cnn_params* p, const dq_cnn_params*
                             const float* x, const dq_cnn_acts* a, dq_cnn_acts* d,
                             const AdamHost& opt = AdamHost{nullptr}, float* head_begin = nullptr,
                             float* head_end = nullptr) {
-  using W16 = Tile<1, 1, 16>;
-  const int K3 = B * 121, K1 = B * 441;
-  const int ch3 = split_chunk(K3, kSplitConvW, W16::BKT), nz3 = (K3 + ch3 - 1) / ch3;
-  const int ch1 = split_chunk(K1, kSplitConv1W, W16::BKT), nz1 = (K1 + ch1 - 1) / ch1;
-  const size_t o3 = c.take((size_t)nz3 * 64 * (Conv3::K + 1));
-  const size_t o2 = c.take((size_t)nz3 * 64 * (Conv2::K + 1));
-  const size_t o1 = c.take((size_t)nz1 * 32 * (Conv1::K + 1));
-  float* ws = c.ws;
+  const BwdOps b(c, p, g, B, x, a, nullptr, d);
   if (c.dry) return;
-  auto dX_c3 = gemm_op<1, 1, 16>(Col2im<Conv3>{d->a3}, WeightT<Conv3>{p->conv3_w},
-                                 EpiMask{d->a2, a->a2, 64}, K3, 64, Conv3::K, Conv3::K);
-  auto dW_c3 = gemm_op<1, 1, 16>(DyT<64>{d->a3}, Im2colT<Conv3>{a->a2},
-                                 EpiPartial{ws + o3, 64, Conv3::K + 1}, 64, Conv3::K + 1, K3, ch3);
-  auto sum_c3 = ReduceOp<EpiGrad>{ws + o3, nz3, 64, Conv3::K + 1,
-                                  EpiGrad{g->conv3_w, g->conv3_b, Conv3::K}};
-  auto dW_c2 = gemm_op<1, 1, 16>(DyT<64>{d->a2}, Im2colT<Conv2>{a->a1},
-                                 EpiPartial{ws + o2, 64, Conv2::K + 1}, 64, Conv2::K + 1, K3, ch3);
-  auto sum_c2 = ReduceOp<EpiGrad>{ws + o2, nz3, 64, Conv2::K + 1,
-                                  EpiGrad{g->conv2_w, g->conv2_b, Conv2::K}};
-  auto dW_c1 = gemm_op<1, 1, 16>(DyT<32>{d->a1}, Im2colT<Conv1>{x},
-                                 EpiPartial{ws + o1, 32, Conv1::K + 1}, 32, Conv1::K + 1, K1, ch1);
-  auto sum_c1 = ReduceOp<EpiGrad>{ws + o1, nz1, 32, Conv1::K + 1,
-                                  EpiGrad{g->conv1_w, g->conv1_b, Conv1::K}};
+  auto part = [&](float* w0, float* w1) { return opt_part<kOpt>(p, g, opt, w0, w1); };
+  float* hm = head_begin + (((head_end - head_begin) / 2) & ~(int64_t)3);
   // (the sub-pixel tiles unpaired here: two per block measured a tie for IQN)
-  if constexpr (kOpt == 0) {
-    group(c, dW_c3, dX_c3);
-    group(c, dW_c2, subpix_op<0, 0>(p, a, d, B), subpix_op<0, 1>(p, a, d, B),
-          subpix_op<1, 0>(p, a, d, B), subpix_op<1, 1>(p, a, d, B), sum_c3);
-    group(c, dW_c1, sum_c2);
-    group(c, sum_c1);
-  } else {
-    using GE = GradEpi<kOpt>;
-    auto part = [&](float* w0, float* w1) { return OptPart<kOpt>::make(p, g, opt.a, w0, w1); };
-    float* hm = head_begin + (((head_end - head_begin) / 2) & ~(int64_t)3);
-    auto sum_c2o = ReduceOp<decltype(GE::make(0, 0, 0, 0, 0, opt, 0))>{
-        ws + o2, nz3, 64, Conv2::K + 1,
-        GE::make(g->conv2_w, g->conv2_b, Conv2::K, p->conv2_w, p->conv2_b, opt, 0)};
-    auto sum_c1o = ReduceOp<decltype(GE::make(0, 0, 0, 0, 0, opt, 0))>{
-        ws + o1, nz1, 32, Conv1::K + 1,
-        GE::make(g->conv1_w, g->conv1_b, Conv1::K, p->conv1_w, p->conv1_b, opt, 1)};
-    group(c, dW_c3, dX_c3, part(head_begin, hm));
-    group(c, dW_c2, subpix_op<0, 0>(p, a, d, B), subpix_op<0, 1>(p, a, d, B),
-          subpix_op<1, 0>(p, a, d, B), subpix_op<1, 1>(p, a, d, B), sum_c3,
-          part(hm, head_end));
-    group(c, dW_c1, sum_c2o, part(p->conv3_w, head_begin));
-    group(c, sum_c1o);
-  }
+  launch(c, NoRider{}, b.dW_c3(), b.dX_c3(), part(head_begin, hm));
+  launch(c, NoRider{}, b.dW_c2(), b.subpix(), b.sum_c3(), part(hm, head_end));
+  launch(c, NoRider{}, b.dW_c1(), b.sum_c2<kOpt>(opt), part(p->conv3_w, head_begin));
+  launch(c, NoRider{}, b.sum_c1<kOpt>(opt));
 }
 
 // Backward in 7 grouped launches (numbered 0..6 below):
@@ -1310,175 +1457,64 @@ void backward_grouped(Ctx& c, const dq_cnn_params* p, const dq_cnn_params* g, in
                       const AdamHost& opt, int first = 0, int last = 7,
                       const RiderDesc* riders = nullptr, int n_riders = 0,
                       const FwdOps* head = nullptr) {
-  const int NO = p->n_out;
-  using GE = GradEpi<kOpt>;
-  using W16 = Tile<1, 1, 16>;
-  // workspace regions (ops of one launch never share one)
-  const int K3 = B * 121, K1 = B * 441;
-  const int ch3 = split_chunk(K3, kSplitConvW, W16::BKT), nz3 = (K3 + ch3 - 1) / ch3;
-  const int ch1 = split_chunk(K1, kSplitConv1W, W16::BKT), nz1 = (K1 + ch1 - 1) / ch1;
-  const size_t o3 = c.take((size_t)nz3 * 64 * (Conv3::K + 1));
-  const size_t o2 = c.take((size_t)nz3 * 64 * (Conv2::K + 1));
-  const size_t o1 = c.take((size_t)nz1 * 32 * (Conv1::K + 1));
-  float* ws = c.ws;
+  const BwdOps b(c, p, g, B, x, a, dout, d);
   if (c.dry) return;
-  auto dX_fc2 = gemm_op<1, 1, 16>(RowKScalar{dout, NO}, ColK{p->fc2_w, kHidden},
-                                  EpiMask{d->h, a->h, kHidden}, B, kHidden, NO, NO);
-  auto dW_fc2 = gemm_op<4, 4, 1>(ColKScalar{dout, NO}, ColKOnes{a->h, kHidden},
-                                 EpiGrad{g->fc2_w, g->fc2_b, kHidden},
-                                 NO, kHidden + 1, B, B);
-  auto dX_fc1 = gemm_op<1, 1, 16, kB1Late, kHidden, kFlat>(RowK{d->h, kHidden}, ColK{p->fc1_w, kFlat},
-                                  EpiMask{d->a3, a->a3, kFlat}, B, kFlat, kHidden, kHidden);
-  auto dW_fc1 = gemm_op<4, 4, 1>(ColK{d->h, kHidden}, ColKOnes{a->a3, kFlat},
-                                 EpiGrad{g->fc1_w, g->fc1_b, kFlat},
-                                 kHidden, kFlat + 1, B, B);
-  auto dX_c3 = gemm_op<1, 1, 16>(Col2im<Conv3>{d->a3}, WeightT<Conv3>{p->conv3_w},
-                                 EpiMask{d->a2, a->a2, 64}, K3, 64, Conv3::K, Conv3::K);
-  auto dW_c3 = gemm_op<1, 1, 16>(DyT<64>{d->a3}, Im2colT<Conv3>{a->a2},
-                                 EpiPartial{ws + o3, 64, Conv3::K + 1}, 64, Conv3::K + 1, K3, ch3);
-  // two of the 8-wave sub-pixel tiles per 16-wave block of the grouped launch (+0.7%)
-  auto sp_op = [](auto op) { return PairOp<decltype(op)>{op}; };
-  auto sp00 = sp_op(subpix_op<0, 0>(p, a, d, B));
-  auto sp01 = sp_op(subpix_op<0, 1>(p, a, d, B));
-  auto sp10 = sp_op(subpix_op<1, 0>(p, a, d, B));
-  auto sp11 = sp_op(subpix_op<1, 1>(p, a, d, B));
-  auto sum_c3 = ReduceOp<EpiGrad>{ws + o3, nz3, 64, Conv3::K + 1,
-                                  EpiGrad{g->conv3_w, g->conv3_b, Conv3::K}};
-  auto dW_c2 = gemm_op<1, 1, 16>(DyT<64>{d->a2}, Im2colT<Conv2>{a->a1},
-                                 EpiPartial{ws + o2, 64, Conv2::K + 1}, 64, Conv2::K + 1, K3, ch3);
-  auto sum_c2 = ReduceOp<EpiGrad>{ws + o2, nz3, 64, Conv2::K + 1,
-                                  EpiGrad{g->conv2_w, g->conv2_b, Conv2::K}};
-  auto dW_c1 = gemm_op<1, 1, 16>(DyT<32>{d->a1}, Im2colT<Conv1>{x},
-                                 EpiPartial{ws + o1, 32, Conv1::K + 1}, 32, Conv1::K + 1, K1, ch1);
-  auto sum_c1 = ReduceOp<decltype(GE::make(0, 0, 0, 0, 0, opt, 0))>{
-      ws + o1, nz1, 32, Conv1::K + 1,
-      GE::make(g->conv1_w, g->conv1_b, Conv1::K, p->conv1_w, p->conv1_b, opt, 1)};
   auto in = [&](int i) { return first <= i && i < last; };
   auto rd = [&](int i) {   // rider of launch i
     return i >= first && i - first < n_riders ? riders + (i - first) : nullptr;
   };
-  if constexpr (kOpt != 0) {
-    {
-      // The optimizer spread over the launches after each gradient is final and each
-      // weight's last read.
-      auto part = [&](float* w0, float* w1) { return OptPart<kOpt>::make(p, g, opt.a, w0, w1); };
-      float* f0 = p->fc1_w;
-      float* f3 = p->fc2_w;                          // fc1_w .. fc1_b (+ pad)
-      // fc1's range op split points (kHeadFrom < 5), in 24ths of the range: thirds
-      float* f1 = f0 + (((f3 - f0) * 8 / 24) & ~(int64_t)3);
-      float* f2 = f0 + (((f3 - f0) * 16 / 24) & ~(int64_t)3);
-      if constexpr (kHeadFrom >= 5) {
-        // fc1 and fc2: TF1 Adam / RMSProp in their weight-gradient GEMMs' vector epilogues,
-        // launch 2 (fc1's instead of range ops over fc1 in launches 3-5 reading the stored
-        // gradient back: +0.6-1.2%; fc2's moved there from launch 1 so launch 1 keeps only
-        // dX fc1 (+ rider), one round of blocks: +0.8%).  conv2 and conv1 in
-        // their split-K sums' epilogues, conv3 as a range op in the last launch.
-        auto dW_fc1a = gemm_op<4, 4, 1>(ColK{d->h, kHidden}, ColKOnes{a->a3, kFlat},
-                                        Fc1EpiOpt<kOpt>::make(p, g, opt.a), kHidden, kFlat + 1,
-                                        B, B);
-        auto dW_fc2a = gemm_op<4, 4, 1>(ColKScalar{dout, NO}, ColKOnes{a->h, kHidden},
-                                        Fc2EpiOpt<kOpt>::make(p, g, opt.a), NO, kHidden + 1, B, B);
-        auto sum_c2a = ReduceOp<decltype(GE::make(0, 0, 0, 0, 0, opt, 0))>{
-            ws + o2, nz3, 64, Conv2::K + 1,
-            GE::make(g->conv2_w, g->conv2_b, Conv2::K, p->conv2_w, p->conv2_b, opt, 0)};
-        if (in(0)) group_r(c, rd(0), dX_fc2);
-        if (in(1)) group_r(c, rd(1), dX_fc1);
-        if (in(2)) group_r(c, rd(2), dW_fc1a, dX_c3, dW_fc2a);
-        if (kHeadFrom == 6) {
-          // conv2's weight-gradient slabs (they need only da2) beside conv3's in launch 3
-          // (+0.9%), the head's conv1 in launch 5, its conv2 and conv3 in the next forward.
-          // (Launch 3 with the sub-pixel tiles first: 19.6 instead of 17.0 us -- conv3's last
-          // slabs then wait for the sub-pixel tiles' slots, tools/group_stamps.py)
-          if (in(3)) group_r(c, rd(3), dW_c3, sp00, sp01, sp10, sp11, dW_c2);
-          if (in(4)) group_r(c, rd(4), sum_c3, dW_c1);
-          if (in(5)) {
-            if (head)
-              group_r(c, rd(5), sum_c2a, sum_c1, part(p->conv3_w, p->fc1_w), head->conv1());
-            else
-              group_r(c, rd(5), sum_c2a, sum_c1, part(p->conv3_w, p->fc1_w));
-          }
-          return;
-        }
-        // five launches: conv2's input gradient by sub-pixel class needs only da2, so conv1's
-        // weight-gradient slabs join launch 4 and the split-K sums end the backward in launch 5
-        if (in(3)) group_r(c, rd(3), dW_c3, sp00, sp01, sp10, sp11);
-        if (head) {
-          if (in(4)) group_r(c, rd(4), sum_c3, dW_c2, dW_c1, head->conv1());
-          if (in(5))
-            group_r(c, rd(5), sum_c2a, sum_c1, part(p->conv3_w, p->fc1_w), head->conv2());
-        } else {
-          if (in(4)) group_r(c, rd(4), sum_c3, dW_c2, dW_c1);
-          if (in(5)) group_r(c, rd(5), sum_c2a, sum_c1, part(p->conv3_w, p->fc1_w));
-        }
-        return;
-      }
-      if (in(0)) group_r(c, rd(0), dX_fc2);
-      if (in(1)) group_r(c, rd(1), dW_fc2, dX_fc1);
-      if (in(2)) group_r(c, rd(2), dW_fc1, dX_c3, part(p->fc2_w, p->fc2_b + NO));
-      if (head) {
-if constexpr (kHeadFrom == 4) {
-          if (in(3)) group_r(c, rd(3), dW_c3, sp00, sp01, sp10, sp11, part(f0, f1));
-          if (in(4)) group_r(c, rd(4), sum_c3, dW_c2, part(f1, f2), head->conv1());
-          if (in(5)) group_r(c, rd(5), sum_c2, dW_c1, part(f2, f3), head->conv2());
-          if (in(6)) group_r(c, rd(6), sum_c1, part(p->conv2_w, p->fc1_w), head->conv3<kB6Late>());
-        } else {
-          if (in(3)) group_r(c, rd(3), dW_c3, sp00, sp01, sp10, sp11, part(f0, f1), head->conv1());
-          if (in(4)) group_r(c, rd(4), sum_c3, dW_c2, part(f1, f2), head->conv2());
-          if (in(5)) group_r(c, rd(5), sum_c2, dW_c1, part(f2, f3), head->conv3());
-          if (in(6)) group_r(c, rd(6), sum_c1, part(p->conv2_w, p->fc1_w), head->fc1());
-        }
-        return;
-      }
-      if (in(3)) group_r(c, rd(3), dW_c3, sp00, sp01, sp10, sp11, part(f0, f1));
-      if (in(4)) group_r(c, rd(4), sum_c3, dW_c2, part(f1, f2));
-      if (in(5)) group_r(c, rd(5), sum_c2, dW_c1, part(f2, f3));
-      if (in(6)) group_r(c, rd(6), sum_c1, part(p->conv2_w, p->fc1_w));
-      return;
-    }
+  // The optimizer spread over the launches after each gradient is final and each
+  // weight's last read: a range op (absent without an optimizer) ...
+  auto part = [&](float* w0, float* w1) { return opt_part<kOpt>(p, g, opt, w0, w1); };
+  // ... or, in the schedules that end in launch 5 (kHeadFrom >= 5), for fc1 and fc2: TF1 Adam /
+  // RMSProp in their weight-gradient GEMMs' vector epilogues, launch 2 (fc1's instead of
+  // range ops over fc1 in launches 3-5 reading the stored gradient back: +0.6-1.2%; fc2's
+  // moved there from launch 1 so launch 1 keeps only dX fc1 (+ rider), one round of blocks:
+  // +0.8%).  conv2 and conv1 in their split-K sums' epilogues, conv3 as a range
+  // op in the last launch.
+  constexpr bool kEpi = kOpt != 0 && kHeadFrom >= 5, kRange = kOpt != 0 && kHeadFrom < 5;
+  constexpr int kFcOpt = kEpi ? kOpt : 0;
+  if (in(0)) launch(c, rd(0), b.dX_fc2());
+  if (in(1)) launch(c, rd(1), when<!kEpi>(b.dW_fc2()), b.dX_fc1());
+  if (in(2))
+    launch(c, rd(2), b.dW_fc1<kFcOpt>(opt), b.dX_c3(), when<kRange>(part(p->fc2_w, p->fc2_b + b.NO)),
+           when<kEpi>(b.dW_fc2<kFcOpt>(opt)));
+  if constexpr (kHeadFrom == 6) {
+    // conv2's weight-gradient slabs (they need only da2) beside conv3's in launch 3
+    // (+0.9%), the head's conv1 in launch 5, its conv2 and conv3 in the next forward.
+    // (Launch 3 with the sub-pixel tiles first: 19.6 instead of 17.0 us -- conv3's last
+    // slabs then wait for the sub-pixel tiles' slots, tools/group_stamps.py)
+    if (in(3)) launch(c, rd(3), b.dW_c3(), b.subpix_pairs(), b.dW_c2());
+    if (in(4)) launch(c, rd(4), b.sum_c3(), b.dW_c1());
+    if (in(5))
+      launch(c, rd(5), b.sum_c2<kOpt>(opt), b.sum_c1<kOpt>(opt), part(p->conv3_w, p->fc1_w),
+             head_layer<0>(head));
+  } else if constexpr (kHeadFrom == 5) {
+    // five launches: conv2's input gradient by sub-pixel class needs only da2, so conv1's
+    // weight-gradient slabs join launch 4 and the split-K sums end the backward in launch 5;
+    // the head's conv1, conv2 in launches 4, 5
+    if (in(3)) launch(c, rd(3), b.dW_c3(), b.subpix_pairs());
+    if (in(4)) launch(c, rd(4), b.sum_c3(), b.dW_c2(), b.dW_c1(), head_layer<0>(head));
+    if (in(5))
+      launch(c, rd(5), b.sum_c2<kOpt>(opt), b.sum_c1<kOpt>(opt), part(p->conv3_w, p->fc1_w),
+             head_layer<1>(head));
+  } else {
+    // seven launches: the head's layers from launch kHeadFrom on (3: conv1 .. the fc1 slabs,
+    // 4: conv1 .. conv3), fc1's range op in thirds over launches 3-5
+    static_assert(kHeadFrom == 3 || kHeadFrom == 4, "kHeadFrom is 3, 4, 5 or 6");
+    float* f0 = p->fc1_w;
+    float* f3 = p->fc2_w;                          // fc1_w .. fc1_b (+ pad)
+    // fc1's range op split points, in 24ths of the range: thirds
+    float* f1 = f0 + (((f3 - f0) * 8 / 24) & ~(int64_t)3);
+    float* f2 = f0 + (((f3 - f0) * 16 / 24) & ~(int64_t)3);
+    constexpr int H = kHeadFrom;
+    if (in(3))
+      launch(c, rd(3), b.dW_c3(), b.subpix_pairs(), part(f0, f1), head_layer<3 - H>(head));
+    if (in(4)) launch(c, rd(4), b.sum_c3(), b.dW_c2(), part(f1, f2), head_layer<4 - H>(head));
+    if (in(5)) launch(c, rd(5), b.sum_c2(), b.dW_c1(), part(f2, f3), head_layer<5 - H>(head));
+    if (in(6))
+      launch(c, rd(6), b.sum_c1<kOpt>(opt), part(p->conv2_w, p->fc1_w), head_layer<6 - H>(head));
   }
-  if (in(0)) group_r(c, rd(0), dX_fc2);
-  if (in(1)) group_r(c, rd(1), dW_fc2, dX_fc1);
-  if (in(2)) group_r(c, rd(2), dW_fc1, dX_c3);
-  if constexpr (kHeadFrom >= 5) {
-    if (kHeadFrom == 6) {            // as the Adam form: conv2's dW slabs in launch 3
-      if (in(3)) group_r(c, rd(3), dW_c3, sp00, sp01, sp10, sp11, dW_c2);
-      if (in(4)) group_r(c, rd(4), sum_c3, dW_c1);
-      if (in(5)) {
-        if (head)
-          group_r(c, rd(5), sum_c2, sum_c1, head->conv1());
-        else
-          group_r(c, rd(5), sum_c2, sum_c1);
-      }
-      return;
-    }
-    if (in(3)) group_r(c, rd(3), dW_c3, sp00, sp01, sp10, sp11);
-    if (head) {
-      if (in(4)) group_r(c, rd(4), sum_c3, dW_c2, dW_c1, head->conv1());
-      if (in(5)) group_r(c, rd(5), sum_c2, sum_c1, head->conv2());
-    } else {
-      if (in(4)) group_r(c, rd(4), sum_c3, dW_c2, dW_c1);
-      if (in(5)) group_r(c, rd(5), sum_c2, sum_c1);
-    }
-    return;
-  }
-  if (head) {
-    if constexpr (kHeadFrom == 4) {
-      if (in(3)) group_r(c, rd(3), dW_c3, sp00, sp01, sp10, sp11);
-      if (in(4)) group_r(c, rd(4), sum_c3, dW_c2, head->conv1());
-      if (in(5)) group_r(c, rd(5), sum_c2, dW_c1, head->conv2());
-      if (in(6)) group_r(c, rd(6), sum_c1, head->conv3());
-    } else {
-      if (in(3)) group_r(c, rd(3), dW_c3, sp00, sp01, sp10, sp11, head->conv1());
-      if (in(4)) group_r(c, rd(4), sum_c3, dW_c2, head->conv2());
-      if (in(5)) group_r(c, rd(5), sum_c2, dW_c1, head->conv3());
-      if (in(6)) group_r(c, rd(6), sum_c1, head->fc1());
-    }
-    return;
-  }
-  if (in(3)) group_r(c, rd(3), dW_c3, sp00, sp01, sp10, sp11);
-  if (in(4)) group_r(c, rd(4), sum_c3, dW_c2);
-  if (in(5)) group_r(c, rd(5), sum_c2, dW_c1);
-  if (in(6)) group_r(c, rd(6), sum_c1);
 }
 
 // The fused Rainbow schedule's backward (backward_grouped<1, 6>, first 1) with the data-
@@ -1492,41 +1528,8 @@ void backward_peer(Ctx& c, const dq_cnn_params* p, const dq_cnn_params* g, int B
                    const dq_cnn_acts* a, const float* dout, dq_cnn_acts* d, const dq_adam_args* oa,
                    const RiderDesc* riders, int n_riders, const FwdOps* head, const dq_peer& P,
                    bool defer_ag) {
-  const int NO = p->n_out;
-  using W16 = Tile<1, 1, 16>;
-  const int K3 = B * 121, K1 = B * 441;
-  const int ch3 = split_chunk(K3, kSplitConvW, W16::BKT), nz3 = (K3 + ch3 - 1) / ch3;
-  const int ch1 = split_chunk(K1, kSplitConv1W, W16::BKT), nz1 = (K1 + ch1 - 1) / ch1;
-  const size_t o3 = c.take((size_t)nz3 * 64 * (Conv3::K + 1));
-  const size_t o2 = c.take((size_t)nz3 * 64 * (Conv2::K + 1));
-  const size_t o1 = c.take((size_t)nz1 * 32 * (Conv1::K + 1));
-  float* ws = c.ws;
+  const BwdOps b(c, p, g, B, x, a, dout, d);
   if (c.dry) return;
-  auto dX_fc1 = gemm_op<1, 1, 16, kB1Late, kHidden, kFlat>(RowK{d->h, kHidden}, ColK{p->fc1_w, kFlat},
-                                           EpiMask{d->a3, a->a3, kFlat}, B, kFlat, kHidden, kHidden);
-  auto dW_fc1 = gemm_op<4, 4, 1>(ColK{d->h, kHidden}, ColKOnes{a->a3, kFlat},
-                                 EpiGrad{g->fc1_w, g->fc1_b, kFlat}, kHidden, kFlat + 1, B, B);
-  auto dW_fc2 = gemm_op<4, 4, 1>(ColKScalar{dout, NO}, ColKOnes{a->h, kHidden},
-                                 EpiGrad{g->fc2_w, g->fc2_b, kHidden}, NO, kHidden + 1, B, B);
-  auto dX_c3 = gemm_op<1, 1, 16>(Col2im<Conv3>{d->a3}, WeightT<Conv3>{p->conv3_w},
-                                 EpiMask{d->a2, a->a2, 64}, K3, 64, Conv3::K, Conv3::K);
-  auto dW_c3 = gemm_op<1, 1, 16>(DyT<64>{d->a3}, Im2colT<Conv3>{a->a2},
-                                 EpiPartial{ws + o3, 64, Conv3::K + 1}, 64, Conv3::K + 1, K3, ch3);
-  auto sp_op = [](auto op) { return PairOp<decltype(op)>{op}; };
-  auto sp00 = sp_op(subpix_op<0, 0>(p, a, d, B));
-  auto sp01 = sp_op(subpix_op<0, 1>(p, a, d, B));
-  auto sp10 = sp_op(subpix_op<1, 0>(p, a, d, B));
-  auto sp11 = sp_op(subpix_op<1, 1>(p, a, d, B));
-  auto sum_c3 = ReduceOp<EpiGrad>{ws + o3, nz3, 64, Conv3::K + 1,
-                                  EpiGrad{g->conv3_w, g->conv3_b, Conv3::K}};
-  auto dW_c2 = gemm_op<1, 1, 16>(DyT<64>{d->a2}, Im2colT<Conv2>{a->a1},
-                                 EpiPartial{ws + o2, 64, Conv2::K + 1}, 64, Conv2::K + 1, K3, ch3);
-  auto sum_c2 = ReduceOp<EpiGrad>{ws + o2, nz3, 64, Conv2::K + 1,
-                                  EpiGrad{g->conv2_w, g->conv2_b, Conv2::K}};
-  auto dW_c1 = gemm_op<1, 1, 16>(DyT<32>{d->a1}, Im2colT<Conv1>{x},
-                                 EpiPartial{ws + o1, 32, Conv1::K + 1}, 32, Conv1::K + 1, K1, ch1);
-  auto sum_c1 = ReduceOp<EpiGrad>{ws + o1, nz1, 32, Conv1::K + 1,
-                                  EpiGrad{g->conv1_w, g->conv1_b, Conv1::K}};
   const AdamDev od{oa->state, oa->slot, oa->lr, oa->beta1, oa->beta2, oa->epsilon, 1};
   // this rank's slice of [lo, n), halves in launches 3 and 4; one float4 per thread
   const int64_t S = (P.n - P.lo) / P.world;
@@ -1542,25 +1545,20 @@ void backward_peer(Ctx& c, const dq_cnn_params* p, const dq_cnn_params* g, int B
   const int nc = std::max(kPubBlocks, blocks_for(P.lo, 2));   // its first blocks publish
   const int na = blocks_for((P.n - P.lo) * (P.world - 1) / P.world, 4);
   auto rd = [&](int i) { return i >= 1 && i - 1 < n_riders ? riders + (i - 1) : nullptr; };
-  group_r(c, rd(1), dX_fc1);
-  group_r(c, rd(2), dW_fc1, dX_c3, dW_fc2);
-  group_r(c, rd(3), PeerPubOp{P, kPeerGrad}, dW_c3, sp00, sp01, sp10, sp11, dW_c2, rs(s0, sm));
-  group_r(c, rd(4), sum_c3, dW_c1, rs(sm, s1));
+  launch(c, rd(1), b.dX_fc1());
+  launch(c, rd(2), b.dW_fc1(), b.dX_c3(), b.dW_fc2());
+  launch(c, rd(3), PeerPubOp{P, kPeerGrad}, b.dW_c3(), b.subpix_pairs(), b.dW_c2(), rs(s0, sm));
+  launch(c, rd(4), b.sum_c3(), b.dW_c1(), rs(sm, s1));
   // launch 5: this rank's slice published, the others' gathered (world 1: nothing to gather;
   // defer_ag: the head of the range (AgParts), the rest by the next forward's conv launches)
   const PeerAgOp ag = defer_ag ? AgParts{&P, oa->var}.head()
                                : PeerAgOp{P, oa->var, na, 0, 0, INT64_MAX};
-  if (P.world > 1)
-    group_r(c, rd(5), PeerPubOp{P, kPeerParam}, sum_c2, sum_c1, ag);
-  else
-    group_r(c, rd(5), PeerPubOp{P, kPeerParam}, sum_c2, sum_c1);
+  launch(c, rd(5), PeerPubOp{P, kPeerParam}, b.sum_c2(), b.sum_c1(),
+         P.world > 1 ? std::optional(ag) : std::nullopt);
   // launch 6: the exchange's blocks first (they publish, then wait), the target head's conv1
   // beside them -- it reads only the target parameters and the batch gathered in launch 4,
   // so its tiles fill the CUs while the exchange waits for the other learners
-  if (head)
-    group(c, PeerExchOp{P, od, oa->var, oa->m, oa->v, nc}, head->conv1());
-  else
-    group(c, PeerExchOp{P, od, oa->var, oa->m, oa->v, nc});
+  launch(c, NoRider{}, PeerExchOp{P, od, oa->var, oa->m, oa->v, nc}, head_layer<0>(head));
 }
 
 // backward_grouped with the runtime head_from (7: the whole target head runs in the next
@@ -1613,12 +1611,74 @@ static int check_adam(const dq_cnn_params* p, const dq_cnn_params* g, const dq_a
   return DQ_OK;
 }
 
+#define DQ_TRY(expr)                   \
+  do {                                 \
+    const int rc_ = (expr);            \
+    if (rc_ != DQ_OK) return rc_;      \
+  } while (0)
+
+// What every entry point checks first: its pointer arguments (args: their conjunction, p
+// among them) and the batch, then the geometry (fc: of a network with its fc layers).
+static int check_net(bool args, int32_t batch, const dq_cnn_params* p, bool fc = true) {
+  DQ_CHECK_ARG(args && batch >= 1, "null argument");
+  DQ_CHECK_ARG(p->in_channels == 4 && (!fc || p->n_out >= 1),
+               "the Nature CNN takes 84x84x4 NHWC input");
+  return DQ_OK;
+}
+// the same for two networks, which run in one launch and so need a workspace each
+static int check_nets(bool args, int32_t batch, const dq_cnn_params* p0, const dq_cnn_params* p1,
+                      const float* ws0, const float* ws1) {
+  DQ_CHECK_ARG(args && batch >= 1, "null argument");
+  DQ_CHECK_ARG(p0->in_channels == 4 && p1->in_channels == 4 && p0->n_out >= 1 && p1->n_out >= 1,
+               "the Nature CNN takes 84x84x4 NHWC input");
+  DQ_CHECK_ARG(ws0 != ws1, "the two networks need separate workspaces");
+  return DQ_OK;
+}
+// a backward's riders, at most `most` (<= 7: one per grouped launch), copied out of the
+// caller's opaque words into r
+static int copy_riders(const dq_rider* riders, int32_t n_riders, int most, const char* too_many,
+                       RiderDesc* r) {
+  DQ_CHECK_ARG(0 <= n_riders && n_riders <= most && (riders || n_riders == 0), too_many);
+  for (int i = 0; i < n_riders; ++i) {
+    memcpy(&r[i], &riders[i], sizeof(RiderDesc));
+    DQ_CHECK_ARG(r[i].kind >= kRiderNone && r[i].kind <= kRiderSetSample, "corrupt rider");
+  }
+  return DQ_OK;
+}
+// the head network riding in a backward over workspace ws: its ops in *hf, *hp = hf (no
+// head: null)
+static int head_ops(const dq_cnn_net* head, const float* ws, int32_t batch, FwdOps* hf,
+                    const FwdOps** hp) {
+  *hp = nullptr;
+  if (!head) return DQ_OK;
+  DQ_CHECK_ARG(head->p && head->x && head->a && head->ws, "null head network field");
+  DQ_CHECK_ARG(head->p->in_channels == 4, "the Nature CNN takes 84x84x4 NHWC input");
+  DQ_CHECK_ARG(head->ws != ws, "the head network needs its own workspace");
+  *hf = FwdOps{head->p, head->x, head->a, head->ws, batch};
+  *hp = hf;
+  return DQ_OK;
+}
+
+static int check_peer(const dq_peer* peer, const float* var) {
+  DQ_CHECK_ARG(peer && var, "null argument");
+  const dq_peer& P = *peer;
+  DQ_CHECK_ARG(P.world >= 1 && P.world <= DQ_PEER_MAX && P.rank >= 0 && P.rank < P.world,
+               "peer: 1 <= world <= DQ_PEER_MAX, 0 <= rank < world");
+  DQ_CHECK_ARG(P.lo >= 0 && P.lo % 4 == 0 && P.n > P.lo && (P.n - P.lo) % (4 * P.world) == 0,
+               "peer: lo % 4 == 0 and (n - lo) % (4 world) == 0");
+  DQ_CHECK_ARG(P.param[P.rank] == var, "peer: var must be this rank's parameter buffer");
+  for (int q = 0; q < P.world; ++q)
+    DQ_CHECK_ARG(P.grad[q] && P.param[q] && P.flags[q], "peer: null rank buffer");
+  DQ_CHECK_ARG(P.max_polls > 0, "peer: max_polls must be positive");
+  DQ_CHECK_ARG(P.xcds >= 0 && P.xcds <= 8, "peer: 0 <= xcds <= 8");
+  return DQ_OK;
+}
+
 extern "C" {
 
 int dq_cnn_forward(const dq_cnn_params* p, int32_t batch, const float* x, dq_cnn_acts* a,
                    float* ws, void* stream) {
-  DQ_CHECK_ARG(p && a && x && ws && batch >= 1, "null argument");
-  DQ_CHECK_ARG(p->in_channels == 4 && p->n_out >= 1, "the Nature CNN takes 84x84x4 NHWC input");
+  DQ_TRY(check_net(p && a && x && ws, batch, p));
   Ctx c{(hipStream_t)stream, ws, false, 0};
   forward(c, p, batch, x, a);
   DQ_CHECK_LAUNCH("dq_cnn_forward");
@@ -1628,10 +1688,7 @@ int dq_cnn_forward(const dq_cnn_params* p, int32_t batch, const float* x, dq_cnn
 int dq_cnn_forward_pair(const dq_cnn_params* p0, const float* x0, dq_cnn_acts* a0, float* ws0,
                         const dq_cnn_params* p1, const float* x1, dq_cnn_acts* a1, float* ws1,
                         int32_t batch, void* stream) {
-  DQ_CHECK_ARG(p0 && a0 && x0 && ws0 && p1 && a1 && x1 && ws1 && batch >= 1, "null argument");
-  DQ_CHECK_ARG(p0->in_channels == 4 && p1->in_channels == 4 && p0->n_out >= 1 && p1->n_out >= 1,
-               "the Nature CNN takes 84x84x4 NHWC input");
-  DQ_CHECK_ARG(ws0 != ws1, "the two networks need separate workspaces");
+  DQ_TRY(check_nets(p0 && a0 && x0 && ws0 && p1 && a1 && x1 && ws1, batch, p0, p1, ws0, ws1));
   Ctx c0{(hipStream_t)stream, ws0, false, 0}, c1{(hipStream_t)stream, ws1, false, 0};
   forward_pair(c0, c1, p0, x0, a0, p1, x1, a1, batch);
   DQ_CHECK_LAUNCH("dq_cnn_forward_pair");
@@ -1640,8 +1697,7 @@ int dq_cnn_forward_pair(const dq_cnn_params* p0, const float* x0, dq_cnn_acts* a
 
 int dq_cnn_forward_head(const dq_cnn_params* p, int32_t batch, const float* x, dq_cnn_acts* a,
                         float* ws, void* stream) {
-  DQ_CHECK_ARG(p && a && x && ws && batch >= 1, "null argument");
-  DQ_CHECK_ARG(p->in_channels == 4 && p->n_out >= 1, "the Nature CNN takes 84x84x4 NHWC input");
+  DQ_TRY(check_net(p && a && x && ws, batch, p));
   Ctx c{(hipStream_t)stream, ws, false, 0};
   forward_head(c, FwdOps{p, x, a, ws, batch});
   DQ_CHECK_LAUNCH("dq_cnn_forward_head");
@@ -1651,10 +1707,7 @@ int dq_cnn_forward_head(const dq_cnn_params* p, int32_t batch, const float* x, d
 int dq_cnn_forward_with_tail(const dq_cnn_params* p0, const float* x0, dq_cnn_acts* a0, float* ws0,
                              const dq_cnn_params* p1, dq_cnn_acts* a1, float* ws1, int32_t batch,
                              void* stream) {
-  DQ_CHECK_ARG(p0 && a0 && x0 && ws0 && p1 && a1 && ws1 && batch >= 1, "null argument");
-  DQ_CHECK_ARG(p0->in_channels == 4 && p1->in_channels == 4 && p0->n_out >= 1 && p1->n_out >= 1,
-               "the Nature CNN takes 84x84x4 NHWC input");
-  DQ_CHECK_ARG(ws0 != ws1, "the two networks need separate workspaces");
+  DQ_TRY(check_nets(p0 && a0 && x0 && ws0 && p1 && a1 && ws1, batch, p0, p1, ws0, ws1));
   Ctx c0{(hipStream_t)stream, ws0, false, 0}, c1{(hipStream_t)stream, ws1, false, 0};
   forward_with_tail(c0, c1, FwdOps{p0, x0, a0, ws0, batch}, FwdOps{p1, nullptr, a1, ws1, batch});
   DQ_CHECK_LAUNCH("dq_cnn_forward_with_tail");
@@ -1664,10 +1717,7 @@ int dq_cnn_forward_with_tail(const dq_cnn_params* p0, const float* x0, dq_cnn_ac
 int dq_cnn_forward_fused(const dq_cnn_params* p0, const float* x0, dq_cnn_acts* a0, float* ws0,
                          const dq_cnn_params* p1, const float* x1, dq_cnn_acts* a1, float* ws1,
                          int32_t batch, int32_t fc1_1, void* stream) {
-  DQ_CHECK_ARG(p0 && a0 && x0 && ws0 && p1 && a1 && ws1 && batch >= 1, "null argument");
-  DQ_CHECK_ARG(p0->in_channels == 4 && p1->in_channels == 4 && p0->n_out >= 1 && p1->n_out >= 1,
-               "the Nature CNN takes 84x84x4 NHWC input");
-  DQ_CHECK_ARG(ws0 != ws1, "the two networks need separate workspaces");
+  DQ_TRY(check_nets(p0 && a0 && x0 && ws0 && p1 && a1 && ws1, batch, p0, p1, ws0, ws1));
   Ctx c0{(hipStream_t)stream, ws0, false, 0}, c1{(hipStream_t)stream, ws1, false, 0};
   DQ_CHECK_ARG((fc1_1 & 12) != 12, "flags 4 (convs only) and 8 (fc layers only) exclude each other");
   DQ_CHECK_ARG(!(fc1_1 & 32) || x1, "flag 32 (net 1's conv1) needs x1");
@@ -1683,10 +1733,7 @@ size_t dq_cnn_fc2_parts_offset(int32_t batch) { return FwdOps::part_offset(batch
 int dq_cnn_forward_fused_c51(const dq_cnn_params* p0, const float* x0, dq_cnn_acts* a0, float* ws0,
                              const dq_cnn_params* p1, dq_cnn_acts* a1, float* ws1, int32_t batch,
                              const dq_c51_target* c51, int32_t flags, void* stream) {
-  DQ_CHECK_ARG(p0 && a0 && x0 && ws0 && p1 && a1 && ws1 && c51 && batch >= 1, "null argument");
-  DQ_CHECK_ARG(p0->in_channels == 4 && p1->in_channels == 4 && p0->n_out >= 1 && p1->n_out >= 1,
-               "the Nature CNN takes 84x84x4 NHWC input");
-  DQ_CHECK_ARG(ws0 != ws1, "the two networks need separate workspaces");
+  DQ_TRY(check_nets(p0 && a0 && x0 && ws0 && p1 && a1 && ws1 && c51, batch, p0, p1, ws0, ws1));
   DQ_CHECK_ARG((flags & 12) != 12, "flags 4 (convs only) and 8 (fc layers only) exclude each other");
   DQ_CHECK_ARG(c51->rewards && c51->terminals && c51->support && c51->m_out, "null C51 argument");
   DQ_CHECK_ARG(c51->num_atoms >= 2 && c51->num_atoms <= 64 && p1->n_out % c51->num_atoms == 0,
@@ -1709,8 +1756,7 @@ int dq_cnn_forward_fused_c51(const dq_cnn_params* p0, const float* x0, dq_cnn_ac
 int dq_cnn_backward(const dq_cnn_params* p, const dq_cnn_params* g, int32_t batch, const float* x,
                     const dq_cnn_acts* a, const float* dout, dq_cnn_acts* d, float* ws,
                     void* stream) {
-  DQ_CHECK_ARG(p && g && a && d && x && dout && ws && batch >= 1, "null argument");
-  DQ_CHECK_ARG(p->in_channels == 4 && p->n_out >= 1, "the Nature CNN takes 84x84x4 NHWC input");
+  DQ_TRY(check_net(p && g && a && d && x && dout && ws, batch, p));
   Ctx c{(hipStream_t)stream, ws, false, 0};
   backward_grouped<0>(c, p, g, batch, x, a, dout, d, AdamHost{nullptr});
   DQ_CHECK_LAUNCH("dq_cnn_backward");
@@ -1720,10 +1766,8 @@ int dq_cnn_backward(const dq_cnn_params* p, const dq_cnn_params* g, int32_t batc
 int dq_cnn_backward_adam(const dq_cnn_params* p, const dq_cnn_params* g, int32_t batch,
                          const float* x, const dq_cnn_acts* a, const float* dout, dq_cnn_acts* d,
                          float* ws, const dq_adam_args* opt, void* stream) {
-  DQ_CHECK_ARG(p && g && a && d && x && dout && ws && opt && batch >= 1, "null argument");
-  DQ_CHECK_ARG(p->in_channels == 4 && p->n_out >= 1, "the Nature CNN takes 84x84x4 NHWC input");
-  const int rc = check_adam(p, g, opt);
-  if (rc != DQ_OK) return rc;
+  DQ_TRY(check_net(p && g && a && d && x && dout && ws && opt, batch, p));
+  DQ_TRY(check_adam(p, g, opt));
   Ctx c{(hipStream_t)stream, ws, false, 0};
   if (opt->kind == DQ_OPT_RMSPROP)
     backward_grouped<2>(c, p, g, batch, x, a, dout, d, AdamHost{opt});
@@ -1736,8 +1780,7 @@ int dq_cnn_backward_adam(const dq_cnn_params* p, const dq_cnn_params* g, int32_t
 int dq_cnn_backward_groups(const dq_cnn_params* p, const dq_cnn_params* g, int32_t batch,
                            const float* x, const dq_cnn_acts* a, const float* dout,
                            dq_cnn_acts* d, float* ws, int32_t first, int32_t last, void* stream) {
-  DQ_CHECK_ARG(p && g && a && d && x && dout && ws && batch >= 1, "null argument");
-  DQ_CHECK_ARG(p->in_channels == 4 && p->n_out >= 1, "the Nature CNN takes 84x84x4 NHWC input");
+  DQ_TRY(check_net(p && g && a && d && x && dout && ws, batch, p));
   DQ_CHECK_ARG(0 <= first && first <= last && last <= 7, "groups must satisfy 0 <= first <= last <= 7");
   Ctx c{(hipStream_t)stream, ws, false, 0};
   backward_grouped<0>(c, p, g, batch, x, a, dout, d, AdamHost{nullptr}, first, last);
@@ -1750,30 +1793,18 @@ int dq_cnn_backward_riders(const dq_cnn_params* p, const dq_cnn_params* g, int32
                            dq_cnn_acts* d, float* ws, const dq_rider* riders, int32_t n_riders,
                            const dq_adam_args* opt, const dq_cnn_net* head, int32_t head_from,
                            int32_t first, int32_t last, void* stream) {
-  DQ_CHECK_ARG(p && g && a && d && x && dout && ws && batch >= 1, "null argument");
-  DQ_CHECK_ARG(p->in_channels == 4 && p->n_out >= 1, "the Nature CNN takes 84x84x4 NHWC input");
-  DQ_CHECK_ARG(0 <= n_riders && n_riders <= 7 && (riders || n_riders == 0),
-               "at most one rider per grouped launch (7)");
+  DQ_TRY(check_net(p && g && a && d && x && dout && ws, batch, p));
+  RiderDesc r[7];
+  DQ_TRY(copy_riders(riders, n_riders, 7, "at most one rider per grouped launch (7)", r));
   DQ_CHECK_ARG(0 <= first && first <= last && last <= 7, "groups must satisfy 0 <= first <= last <= 7");
   DQ_CHECK_ARG(!opt || (first <= 1 && last == 7), "the fused optimizer needs the whole backward");
   DQ_CHECK_ARG(head_from >= 3 && head_from <= 7, "head_from must be in [3, 7]");
-  RiderDesc r[7];
-  for (int i = 0; i < n_riders; ++i) {
-    memcpy(&r[i], &riders[i], sizeof(RiderDesc));
-    DQ_CHECK_ARG(r[i].kind >= kRiderNone && r[i].kind <= kRiderSetSample, "corrupt rider");
-  }
   FwdOps hf{};
-  if (head) {
-    DQ_CHECK_ARG(head->p && head->x && head->a && head->ws, "null head network field");
-    DQ_CHECK_ARG(head->p->in_channels == 4, "the Nature CNN takes 84x84x4 NHWC input");
-    DQ_CHECK_ARG(head->ws != ws, "the head network needs its own workspace");
-    hf = FwdOps{head->p, head->x, head->a, head->ws, batch};
-  }
+  const FwdOps* hp;
+  DQ_TRY(head_ops(head, ws, batch, &hf, &hp));
   Ctx c{(hipStream_t)stream, ws, false, 0};
-  const FwdOps* hp = head ? &hf : nullptr;
   if (opt) {
-    const int rc = check_adam(p, g, opt);
-    if (rc != DQ_OK) return rc;
+    DQ_TRY(check_adam(p, g, opt));
     if (opt->kind == DQ_OPT_RMSPROP)
       backward_head_from<2>(c, p, g, batch, x, a, dout, d, AdamHost{opt}, first, last, r, n_riders,
                             hp, head_from);
@@ -1793,18 +1824,14 @@ int dq_cnn_backward_peer(const dq_cnn_params* p, const dq_cnn_params* g, int32_t
                          dq_cnn_acts* d, float* ws, const dq_rider* riders, int32_t n_riders,
                          const dq_adam_args* opt, const dq_cnn_net* head, const dq_peer* peer,
                          int32_t defer_ag, void* stream) {
-  DQ_CHECK_ARG(p && g && a && d && x && dout && ws && opt && peer && batch >= 1, "null argument");
-  DQ_CHECK_ARG(p->in_channels == 4 && p->n_out >= 1, "the Nature CNN takes 84x84x4 NHWC input");
+  DQ_TRY(check_net(p && g && a && d && x && dout && ws && opt && peer, batch, p));
   DQ_CHECK_ARG(opt->kind == DQ_OPT_ADAM, "the peer exchange applies TF1 Adam");
-  DQ_CHECK_ARG(0 <= n_riders && n_riders <= 5 && (riders || n_riders == 0),
-               "at most one rider per grouped launch 1..5");
-  const int rc = check_adam(p, g, opt);
-  if (rc != DQ_OK) return rc;
+  RiderDesc r[5];
+  DQ_TRY(copy_riders(riders, n_riders, 5, "at most one rider per grouped launch 1..5", r));
+  DQ_TRY(check_adam(p, g, opt));
+  DQ_TRY(check_peer(peer, opt->var));
+  // what the exchange inside the backward asks beyond check_peer
   const dq_peer& P = *peer;
-  DQ_CHECK_ARG(P.world >= 1 && P.world <= DQ_PEER_MAX && P.rank >= 0 && P.rank < P.world,
-               "peer: 1 <= world <= DQ_PEER_MAX, 0 <= rank < world");
-  DQ_CHECK_ARG(P.lo >= 0 && P.lo % 4 == 0 && P.n > P.lo && (P.n - P.lo) % (4 * P.world) == 0,
-               "peer: lo % 4 == 0 and (n - lo) % (4 world) == 0");
   DQ_CHECK_ARG(P.n >= (int64_t)(p->fc2_b + p->n_out - opt->var),
                "peer: [lo, n) must reach the end of the flat parameter buffer");
   // exactly the fc bucket: a head of fc1 floats in the conv bucket would be read by the peers
@@ -1815,47 +1842,17 @@ int dq_cnn_backward_peer(const dq_cnn_params* p, const dq_cnn_params* g, int32_t
                "so that its length divides into 4 world-float slices)");
   DQ_CHECK_ARG(P.param[P.rank] == opt->var && P.grad[P.rank] == g->conv1_w - (p->conv1_w - opt->var),
                "peer: this rank's buffers must be opt->var and the gradient of its layout");
-  for (int q = 0; q < P.world; ++q)
-    DQ_CHECK_ARG(P.grad[q] && P.param[q] && P.flags[q], "peer: null rank buffer");
-  DQ_CHECK_ARG(P.max_polls > 0, "peer: max_polls must be positive");
-  DQ_CHECK_ARG(P.xcds >= 0 && P.xcds <= 8, "peer: 0 <= xcds <= 8");
-  RiderDesc r[5];
-  for (int i = 0; i < n_riders; ++i) {
-    memcpy(&r[i], &riders[i], sizeof(RiderDesc));
-    DQ_CHECK_ARG(r[i].kind >= kRiderNone && r[i].kind <= kRiderSetSample, "corrupt rider");
-  }
   FwdOps hf{};
-  if (head) {
-    DQ_CHECK_ARG(head->p && head->x && head->a && head->ws, "null head network field");
-    DQ_CHECK_ARG(head->p->in_channels == 4, "the Nature CNN takes 84x84x4 NHWC input");
-    DQ_CHECK_ARG(head->ws != ws, "the head network needs its own workspace");
-    hf = FwdOps{head->p, head->x, head->a, head->ws, batch};
-  }
+  const FwdOps* hp;
+  DQ_TRY(head_ops(head, ws, batch, &hf, &hp));
   Ctx c{(hipStream_t)stream, ws, false, 0};
-  backward_peer(c, p, g, batch, x, a, dout, d, opt, r, n_riders, head ? &hf : nullptr, P,
-                defer_ag != 0);
+  backward_peer(c, p, g, batch, x, a, dout, d, opt, r, n_riders, hp, P, defer_ag != 0);
   DQ_CHECK_LAUNCH("dq_cnn_backward_peer");
   return DQ_OK;
 }
 
-static int check_peer(const dq_peer* peer, const float* var) {
-  DQ_CHECK_ARG(peer && var, "null argument");
-  const dq_peer& P = *peer;
-  DQ_CHECK_ARG(P.world >= 1 && P.world <= DQ_PEER_MAX && P.rank >= 0 && P.rank < P.world,
-               "peer: 1 <= world <= DQ_PEER_MAX, 0 <= rank < world");
-  DQ_CHECK_ARG(P.lo >= 0 && P.lo % 4 == 0 && P.n > P.lo && (P.n - P.lo) % (4 * P.world) == 0,
-               "peer: lo % 4 == 0 and (n - lo) % (4 world) == 0");
-  DQ_CHECK_ARG(P.param[P.rank] == var, "peer: var must be this rank's parameter buffer");
-  for (int q = 0; q < P.world; ++q)
-    DQ_CHECK_ARG(P.grad[q] && P.param[q] && P.flags[q], "peer: null rank buffer");
-  DQ_CHECK_ARG(P.max_polls > 0, "peer: max_polls must be positive");
-  DQ_CHECK_ARG(P.xcds >= 0 && P.xcds <= 8, "peer: 0 <= xcds <= 8");
-  return DQ_OK;
-}
-
 int dq_peer_all_gather(const dq_peer* peer, float* var, void* stream) {
-  const int rc = check_peer(peer, var);
-  if (rc != DQ_OK) return rc;
+  DQ_TRY(check_peer(peer, var));
   const dq_peer& P = *peer;
   if (P.world > 1) {
     Ctx c{(hipStream_t)stream, nullptr, false, 0};
@@ -1894,8 +1891,7 @@ int dq_debug_group_read(void* recs, unsigned* seq, unsigned* dims) {
 int dq_peer_selftest(const dq_peer* peer, uint32_t tag, int32_t* mismatches_out, void* stream) {
   DQ_CHECK_ARG(peer && mismatches_out, "null argument");
   const dq_peer& P = *peer;
-  const int rc = check_peer(peer, P.param[P.rank]);
-  if (rc != DQ_OK) return rc;
+  DQ_TRY(check_peer(peer, P.param[P.rank]));
   DQ_CHECK_ARG(P.n % 4 == 0 && P.n / 4 < (int64_t)1 << 27, "peer: n % 4 == 0, buffers < 2 GB");
   Ctx c{(hipStream_t)stream, nullptr, false, 0};
   group(c, SelfTestFillOp{P, tag, 2048});                      // 8 blocks per CU, every XCD
@@ -1909,14 +1905,10 @@ int dq_cnn_forward_fused_peer(const dq_cnn_params* p0, const float* x0, dq_cnn_a
                               const dq_cnn_params* p1, const float* x1, dq_cnn_acts* a1, float* ws1,
                               int32_t batch, int32_t fc1_1, const dq_peer* peer, float* var,
                               void* stream) {
-  DQ_CHECK_ARG(p0 && a0 && x0 && ws0 && p1 && a1 && ws1 && batch >= 1, "null argument");
-  DQ_CHECK_ARG(p0->in_channels == 4 && p1->in_channels == 4 && p0->n_out >= 1 && p1->n_out >= 1,
-               "the Nature CNN takes 84x84x4 NHWC input");
-  DQ_CHECK_ARG(ws0 != ws1, "the two networks need separate workspaces");
+  DQ_TRY(check_nets(p0 && a0 && x0 && ws0 && p1 && a1 && ws1, batch, p0, p1, ws0, ws1));
   DQ_CHECK_ARG((fc1_1 & (4 | 8 | 32)) == 0 && (fc1_1 & 16),
                "the deferred gather rides in the head_from 6 schedule's conv launches (flag 16)");
-  const int rc = check_peer(peer, var);
-  if (rc != DQ_OK) return rc;
+  DQ_TRY(check_peer(peer, var));
   Ctx c0{(hipStream_t)stream, ws0, false, 0}, c1{(hipStream_t)stream, ws1, false, 0};
   const AgParts ag{peer, var};
   forward_fused(c0, c1, FwdOps{p0, x0, a0, ws0, batch}, FwdOps{p1, x1, a1, ws1, batch},
@@ -1928,8 +1920,7 @@ int dq_cnn_forward_fused_peer(const dq_cnn_params* p0, const float* x0, dq_cnn_a
 
 int dq_cnn_forward_torso(const dq_cnn_params* p, int32_t batch, const float* x, dq_cnn_acts* a,
                          float* ws, void* stream) {
-  DQ_CHECK_ARG(p && a && x && ws && batch >= 1, "null argument");
-  DQ_CHECK_ARG(p->in_channels == 4, "the Nature CNN takes 84x84x4 NHWC input");
+  DQ_TRY(check_net(p && a && x && ws, batch, p, false));
   Ctx c{(hipStream_t)stream, ws, false, 0};
   const FwdOps f{p, x, a, ws, batch};
   group(c, f.conv1<false>());
@@ -1942,8 +1933,7 @@ int dq_cnn_forward_torso(const dq_cnn_params* p, int32_t batch, const float* x, 
 int dq_cnn_backward_torso(const dq_cnn_params* p, const dq_cnn_params* g, int32_t batch,
                           const float* x, const dq_cnn_acts* a, dq_cnn_acts* d, float* ws,
                           void* stream) {
-  DQ_CHECK_ARG(p && g && a && d && x && ws && batch >= 1, "null argument");
-  DQ_CHECK_ARG(p->in_channels == 4, "the Nature CNN takes 84x84x4 NHWC input");
+  DQ_TRY(check_net(p && g && a && d && x && ws, batch, p, false));
   Ctx c{(hipStream_t)stream, ws, false, 0};
   backward_torso_grouped(c, p, g, batch, x, a, d);
   DQ_CHECK_LAUNCH("dq_cnn_backward_torso");
@@ -1954,10 +1944,8 @@ int dq_cnn_backward_torso_opt(const dq_cnn_params* p, const dq_cnn_params* g, in
                               const float* x, const dq_cnn_acts* a, dq_cnn_acts* d, float* ws,
                               const dq_adam_args* opt, float* head_begin, float* head_end,
                               void* stream) {
-  DQ_CHECK_ARG(p && g && a && d && x && ws && opt && batch >= 1, "null argument");
-  DQ_CHECK_ARG(p->in_channels == 4, "the Nature CNN takes 84x84x4 NHWC input");
-  const int rc = check_adam(p, g, opt);
-  if (rc) return rc;
+  DQ_TRY(check_net(p && g && a && d && x && ws && opt, batch, p, false));
+  DQ_TRY(check_adam(p, g, opt));
   DQ_CHECK_ARG(head_begin && head_end && head_begin >= p->conv3_b + 64 && head_end > head_begin &&
                    ((head_begin - opt->var) & 3) == 0 && ((p->conv3_w - opt->var) & 3) == 0,
                "head range: 16-byte aligned, after conv3 in opt->var");
@@ -1973,8 +1961,7 @@ int dq_cnn_backward_torso_opt(const dq_cnn_params* p, const dq_cnn_params* g, in
 int dq_cnn_backward_layer(const dq_cnn_params* p, const dq_cnn_params* g, int32_t batch,
                           const float* x, const dq_cnn_acts* a, const float* dout, dq_cnn_acts* d,
                           float* ws, int32_t layer, int32_t part, void* stream) {
-  DQ_CHECK_ARG(p && g && a && d && x && dout && ws && batch >= 1, "null argument");
-  DQ_CHECK_ARG(p->in_channels == 4 && p->n_out >= 1, "the Nature CNN takes 84x84x4 NHWC input");
+  DQ_TRY(check_net(p && g && a && d && x && dout && ws, batch, p));
   Ctx c{(hipStream_t)stream, ws, false, 0};
   DQ_CHECK_ARG((part == 0 || part == 1) && backward_layer(c, p, g, batch, x, a, dout, d, layer, part),
                "layer must be 0..4 (fc2, fc1, conv3, conv2, conv1), part 0 (input grad, not conv1) "
