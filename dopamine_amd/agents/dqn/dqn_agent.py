@@ -153,7 +153,9 @@ class DQNAgent(object):
     self.use_hip_mlp = use_hip_mlp
     self.fuse_optimizer = fuse_optimizer
     self.pair_forward = pair_forward
-    self.ride_replay = ride_replay
+    # a gather that rides in the backward's launches sums the n-step reward left to right,
+    # np.sum's order below 8 steps only: longer horizons take the schedule without riders
+    self.ride_replay = ride_replay and update_horizon < 8
     self.fused_head = fused_head
     self._graph_sets = {}          # pipe -> (graphs per parity, optimizer graphs per parity)
     self._graph_pool = None

@@ -257,9 +257,11 @@ __device__ __forceinline__ int64_t frame_of(const ReplayView& v, const GatherOut
 // float32 (circular_replay_buffer.py:96-183, sampled at :530-548).  One block per
 // sample: L from the terminal store, the action rows copied as bytes, the n-step reward
 // as numpy's np.sum(discount[:L] * trajectory_rewards, axis=0) -- the (L,) float32
-// discount broadcast against the LAST axis of (L,) + reward_shape, products and the
-// left-to-right sum (numpy's axis-0 order) in the promoted type -- then cast to the
-// reward dtype as the assignment into the batch array does.
+// discount broadcast against the LAST axis of (L,) + reward_shape, products and the sum
+// in the promoted type: a shaped reward's rows are added left to right (numpy's axis-0
+// order), a scalar reward's L products as np.sum adds a contiguous 1-D array (left to
+// right below 8 of them, np_sum_wave's order from 8 on) -- then cast to the reward dtype
+// as the assignment into the batch array does.
 // ---------------------------------------------------------------------------
 struct ElemArgs {
   const int32_t* indices;
@@ -329,6 +331,21 @@ __global__ __launch_bounds__(256) void k_gather_elems(ReplayView v, ElemArgs e) 
   const int m = e.rew_last;
   if (m > 0 && L != m && L != 1) {
     if (threadIdx.x == 0) latch(v.meta, DQ_ST_BROADCAST, L, m == 1 ? 1.0 : 0.0);
+    return;
+  }
+  if (m == 0 && L >= 8) {   // a scalar reward (rew_elems == 1), 8 products or more: the first wave
+    if (threadIdx.x >= kWave) return;
+    float f = 0.0f;
+    double d = 0.0;
+    if (e.acc64)
+      d = np_sum_wave<double>(L, [&](int k) {
+        return __dmul_rn((double)v.discount[k], dt_load(e.rew, pymod(idx + k, v.C), e.rew_dt));
+      });
+    else
+      f = np_sum_wave<float>(L, [&](int k) {
+        return __fmul_rn(v.discount[k], (float)dt_load(e.rew, pymod(idx + k, v.C), e.rew_dt));
+      });
+    if (threadIdx.x == 0) dt_store(e.rew_out, b, e.rew_dt, e.acc64 != 0, f, d);
     return;
   }
   for (int j = threadIdx.x; j < e.rew_elems; j += blockDim.x) {
@@ -783,6 +800,9 @@ int dq_replay_record_gather_nhwc(dq_replay* h, const int32_t* indices, int32_t b
   DQ_CHECK_ARG(h->cfg.obs_is_u8, "F32_NHWC layout needs uint8 observations");
   DQ_CHECK_ARG(h->cfg.stack_size == 4, "F32_NHWC layout needs stack_size == 4");
   DQ_CHECK_ARG((h->cfg.obs_bytes & 3) == 0, "F32_NHWC layout needs obs_bytes % 4 == 0");
+  // the riders' scalars sum left to right (write_scalars_wave_short): np.sum's order below 8
+  DQ_CHECK_ARG(h->cfg.update_horizon < 8,
+               "a recorded gather needs update_horizon < 8 (launch dq_replay_gather instead)");
   RiderDesc r{};
   r.kind = kRiderGatherNhwc;
   r.batch = batch;

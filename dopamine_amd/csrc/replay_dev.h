@@ -406,14 +406,142 @@ __device__ __forceinline__ int64_t stack_base(const ReplayView& v, const GatherO
   return base;
 }
 
+__device__ __forceinline__ float add_rn(float a, float b) { return __fadd_rn(a, b); }
+__device__ __forceinline__ double add_rn(double a, double b) { return __dadd_rn(a, b); }
+
+// np.sum of the contiguous 1-D array x(0) .. x(L - 1), L >= 8, in numpy's own order (its
+// pairwise_sum), which is NOT left to right from 8 elements on:
+//   * up to 128 elements: eight accumulators r[j] start from x(j) and take x(i + j) over the
+//     whole groups of 8, combine as ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), and the L % 8
+//     leftovers are then added one by one;
+//   * more: split at n2 = L/2 rounded down to a multiple of 8, sum(first n2) + sum(rest),
+//     recursively.
+// Run by one whole wave (every lane gets the result): lanes 0..7 are the accumulators, and
+// lane d keeps frame d of the recursion (depth < 32: L < 2^31), so there is no stack in
+// scratch and nothing here costs the callers more than a few registers.  Cold: the
+// workloads' update horizons are below 8.
+template <typename T, typename X>
+__device__ __forceinline__ T np_sum_wave(int L, X x) {
+  const int lane = threadIdx.x & 63;
+  int f_lo = 0, f_n = 0, f_right = 0;   // this lane's frame: the right half still to do ...
+  T f_sum = 0;                          // ... or (f_right) the left half's sum
+  int sp = 0, lo = 0, n = L;
+  T acc = 0;
+  for (;;) {
+    while (n > 128) {                   // descend into the left halves
+      int n2 = n / 2;
+      n2 -= n2 % 8;
+      if (lane == sp) {
+        f_lo = lo + n2;
+        f_n = n - n2;
+        f_right = 0;
+      }
+      ++sp;
+      n = n2;
+    }
+    const int whole = n - n % 8;        // a block of 8 .. 128 elements
+    T r = 0;
+    if (lane < 8) {
+      r = x(lo + lane);
+      for (int i = 8; i < whole; i += 8) r = add_rn(r, x(lo + i + lane));
+    }
+    r = add_rn(r, __shfl_down(r, 1));   // lanes 0, 2, 4, 6: r0+r1, r2+r3, r4+r5, r6+r7
+    r = add_rn(r, __shfl_down(r, 2));   // lanes 0, 4
+    r = add_rn(r, __shfl_down(r, 4));   // lane 0
+    acc = __shfl(r, 0);
+    for (int i = whole; i < n; ++i) acc = add_rn(acc, x(lo + i));
+    for (;;) {                          // ascend: acc is the sum of a finished subtree
+      if (sp == 0) return acc;
+      const int top = sp - 1;
+      if (__shfl(f_right, top) == 0) {  // it was a left half: keep it, do the right half
+        if (lane == top) {
+          f_sum = acc;
+          f_right = 1;
+        }
+        lo = __shfl(f_lo, top);
+        n = __shfl(f_n, top);
+        break;
+      }
+      acc = add_rn(__shfl(f_sum, top), acc);
+      sp = top;
+    }
+  }
+}
+
 // Per-sample scalars (crb:517-555), one wave: lanes load the trajectory's
-// terminal/reward bytes in parallel, the ballot finds L, lane 0 sums the
-// float32 products left to right exactly as numpy's n < 8 reduction does.
+// terminal/reward bytes in parallel, the ballot finds L, and the float32 products are
+// summed as np.sum sums them: left to right below 8 of them (numpy's n < 8 reduction),
+// in np_sum_wave's order from 8 on.
 // Loads that need L (next_action/next_reward at idx + L) are issued for the
 // usual L = n together with the trajectory and re-read only when a terminal
 // cuts it short, so the wave waits on two dependent loads (index, then
 // everything else), not three.
 __device__ inline void write_scalars_wave(const ReplayView& v, const GatherOut& g, int b,
+                                          int64_t idx) {
+  const int lane = threadIdx.x & 63;
+  float p = 0.0f;
+  bool t = false;
+  // independent of L: issued with the trajectory
+  const int64_t nspec = pymod(idx + v.n, v.C);
+  int32_t a0 = 0, na = 0;
+  float nr = 0.0f, pr = 0.0f;
+  if (lane == 0) {
+    a0 = v.actions[idx];
+    na = v.actions[nspec];
+    nr = v.rewards[nspec];
+    if (g.probs) pr = (float)v.tree[((int64_t)1 << v.depth) - 1 + idx];
+  }
+  if (lane < v.n) {
+    const int64_t j = pymod(idx + lane, v.C);
+    t = v.terminals[j] != 0;
+    p = __fmul_rn(v.discount[lane], v.rewards[j]);
+  }
+  int L = v.n;
+  bool term = false;
+  const uint64_t tm = __ballot(t);
+  if (tm) {
+    L = __ffsll((unsigned long long)tm);
+    term = true;
+  }
+  // a horizon longer than a wave: the later 64-step windows, until a terminal shows
+  for (int j0 = kWave; j0 < v.n && !term; j0 += kWave) {
+    const uint64_t m =
+        __ballot(j0 + lane < v.n && v.terminals[pymod(idx + j0 + lane, v.C)] != 0);
+    if (m) {
+      L = j0 + __ffsll((unsigned long long)m);
+      term = true;
+    }
+  }
+  float acc = 0.0f;
+  if (L < 8) {
+    for (int k = 0; k < L; ++k) acc = __fadd_rn(acc, __shfl(p, k));
+  } else {
+    acc = np_sum_wave<float>(L, [&](int k) {
+      return __fmul_rn(v.discount[k], v.rewards[pymod(idx + k, v.C)]);
+    });
+  }
+  if (lane == 0) {
+    if (L != v.n) {     // a terminal ended the trajectory early: the loads at idx + L
+      const int64_t nxt = pymod(idx + L, v.C);
+      na = v.actions[nxt];
+      nr = v.rewards[nxt];
+    }
+    if (g.action) g.action[b] = a0;
+    if (g.reward) g.reward[b] = acc;
+    if (g.next_action) g.next_action[b] = na;
+    if (g.next_reward) g.next_reward[b] = nr;
+    if (g.terminal) g.terminal[b] = term ? 1 : 0;
+    if (g.indices_out) g.indices_out[b] = (int32_t)idx;
+    if (g.probs) g.probs[b] = pr;
+  }
+}
+
+// write_scalars_wave for update horizons below 8, where np.sum's order IS left to right: the
+// form that rides in the CNN's grouped launches (gather_nhwc4_body's kScalEarly / kScalLate).
+// Those launches' GEMM tiles are held to 64 VGPRs and their register allocation moves with
+// any code added here, so this body stays as it is and dq_replay_record_gather_nhwc refuses
+// a buffer whose update_horizon is 8 or more (its gather is launched on its own).
+__device__ inline void write_scalars_wave_short(const ReplayView& v, const GatherOut& g, int b,
                                           int64_t idx) {
   const int lane = threadIdx.x & 63;
   float p = 0.0f;
@@ -533,14 +661,14 @@ __device__ __forceinline__ void gather_nhwc4_body(const ReplayView& v, const Gat
   constexpr bool kLateScalars = kScalars == kScalLate;
   const int b = slot >> 1, which = slot & 1;
   const bool scal = kScalars != kScalNone && bx == 0 && which == 0 && tid < 64;
-  if (!kLateScalars && scal) write_scalars_wave(v, g, b, pymod((int64_t)g.indices[b], v.C));
+  if (!kLateScalars && scal) write_scalars_wave_short(v, g, b, pymod((int64_t)g.indices[b], v.C));
   float* dst_base = (float*)(which ? g.next_state : g.state);
   const int64_t nd = v.obs_bytes >> 2;
   const int lane = tid & 63;
   // this wave's R x 64 dwords of each of the 4 frames
   const int64_t w0 = ((int64_t)bx * 256 + (tid & ~63)) * R;
   if (!dst_base || w0 >= nd) {
-    if (kLateScalars && scal) write_scalars_wave(v, g, b, pymod((int64_t)g.indices[b], v.C));
+    if (kLateScalars && scal) write_scalars_wave_short(v, g, b, pymod((int64_t)g.indices[b], v.C));
     return;
   }
   // next_state's stack ends at idx + L (L = n-step length, crb:517-531).  Its
@@ -570,7 +698,7 @@ __device__ __forceinline__ void gather_nhwc4_body(const ReplayView& v, const Gat
     if (base != spec) load(base);
   } else {
     load(idx);
-    if (kLateScalars && scal) write_scalars_wave(v, g, b, idx);
+    if (kLateScalars && scal) write_scalars_wave_short(v, g, b, idx);
   }
   if (gp) GP_STAMP(gp, 2);
   // store j of chunk r: lane l writes pixel 64j + l of the chunk (its 4 channels =

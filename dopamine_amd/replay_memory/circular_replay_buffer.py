@@ -605,9 +605,11 @@ class OutOfGraphReplayBuffer(object):
     p = _lib.ptr
     if self._riders is not None:
       if (layout != _lib.LAYOUT_F32_NHWC or self._extra_storage_types or self._generic_action or
-          self._generic_reward):
+          self._generic_reward or self._update_horizon >= 8):
+        # update_horizon: a rider sums the n-step reward left to right, which is np.sum's
+        # order (crb:540-541) below 8 products only
         raise ValueError('only the NHWC gather (no extra storage, scalar int32 action and '
-                         'float32 reward) can be recorded as a rider')
+                         'float32 reward, update_horizon < 8) can be recorded as a rider')
       r = _lib.Rider()
       _lib.call('dq_replay_record_gather_nhwc', self._h, p(d_idx), batch_size, p(out['state']),
                 p(out['next_state']), p(out['action']), p(out['reward']), p(out['next_action']),

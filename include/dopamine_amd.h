@@ -154,8 +154,10 @@ int dq_replay_gather(dq_replay* h, const int32_t* indices, int32_t batch, int32_
  *   reward_out[b] = sum over i < L of disc * rewards[(idx + i) % C], numpy's
  *     np.sum(discount[:L] * trajectory_rewards, axis=0): the (L,) float32 discount vector
  *     broadcasts against the LAST axis of (L,) + reward_shape (reward_last = its size, 0 for
- *     a scalar reward), products and the left-to-right sum in float64 when acc_f64 (numpy's
- *     float32 x reward_dtype promotion) else float32, then cast to reward_dtype;
+ *     a scalar reward), products and the sum in float64 when acc_f64 (numpy's float32 x
+ *     reward_dtype promotion) else float32, in np.sum's order -- a shaped reward's rows left
+ *     to right, a scalar reward's L products left to right below 8 of them and pairwise
+ *     (numpy's pairwise_sum) from 8 on -- then cast to reward_dtype;
  *   next_reward_out[b] = rewards[(idx + L) % C].
  * reward_dtype: DQ_DT_*; reward_elems = prod(reward_shape).  A sample whose L does not
  * broadcast latches DQ_ST_BROADCAST.  Any output pointer may be NULL. */

@@ -113,10 +113,52 @@ def invalid_range(cursor, capacity, stack_size, update_horizon):
                    for k in range(stack_size + update_horizon)])
 
 
+def sum_left_to_right(x):
+  """The sum of a 1-D float array taken left to right in its own type.  numpy's order below
+  8 elements only; kept so the tests can show that it is NOT np.sum's order from 8 on."""
+  x = np.asarray(x)
+  acc = x.dtype.type(0.0)
+  for v in x:
+    acc = x.dtype.type(acc + v)
+  return acc
+
+
+def numpy_sum_order(x):
+  """np.sum of a contiguous 1-D float32 / float64 array, restated add by add (numpy's
+  pairwise_sum, umath loops): below 8 elements left to right; up to 128 elements eight
+  accumulators r[j] start from x[j] and take x[i + j] over whole groups of 8, combine as
+  ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), then the n % 8 leftovers are added one by one; longer
+  arrays split at n2 = n/2 rounded down to a multiple of 8 and add the two halves' sums.
+  Pinned to the installed numpy by tests/test_replay_edges_reference_cpu.py (n = 1..300)."""
+  x = np.asarray(x)
+  t = x.dtype.type
+  n = len(x)
+  if n < 8:
+    return sum_left_to_right(x)
+  if n <= 128:
+    r = [x[j] for j in range(8)]
+    i = 8
+    while i < n - n % 8:
+      for j in range(8):
+        r[j] = t(r[j] + x[i + j])
+      i += 8
+    res = t(t(t(r[0] + r[1]) + t(r[2] + r[3])) + t(t(r[4] + r[5]) + t(r[6] + r[7])))
+    for k in range(i, n):
+      res = t(res + x[k])
+    return res
+  n2 = n // 2
+  n2 -= n2 % 8
+  return t(numpy_sum_order(x[:n2]) + numpy_sum_order(x[n2:]))
+
+
 # --------------------------------------------------------------------------
 # Uniform circular buffer (crb:80-591)
 # --------------------------------------------------------------------------
 class ReplayOracle:
+  # the scalar float32 n-step reward's summation order (crb:540-541 np.sum); a test swaps in
+  # sum_left_to_right on an instance to show that the goldens tell the two orders apart
+  sum_order = staticmethod(numpy_sum_order)
+
   def __init__(self, observation_shape, stack_size, replay_capacity, batch_size,
                update_horizon=1, gamma=0.99, max_sample_attempts=1000,
                observation_dtype=np.uint8, terminal_dtype=np.uint8,
@@ -236,10 +278,8 @@ class ReplayOracle:
       # crb:540-541 as written: the (L,) float32 discount broadcast against (L,) +
       # reward_shape (numpy raises where it does not), summed over axis 0
       return np.sum(self.discount[:L] * r, axis=0), term, L
-    acc = np.float32(0.0)
-    for k in range(L):  # float32 products summed left to right (numpy n<8 loop)
-      acc = np.float32(acc + np.float32(self.discount[k] * r[k]))
-    return acc, term, L
+    prod = np.array([np.float32(self.discount[k] * r[k]) for k in range(L)], np.float32)
+    return self.sum_order(prod), term, L
 
   def sample_transition_batch(self, batch_size=None, indices=None):
     B = self.B if batch_size is None else batch_size

@@ -6,7 +6,8 @@ stand-ins are for non-algorithmic imports that are absent here:
 ``tensorflow`` (only ``tf.logging.info`` is touched by the code paths used)
 and ``gin`` / ``gin.tf`` (``@gin.configurable`` treated as identity).
 
-Outputs: tests/golden/{sumtree,replay_uniform,replay_per}.npz -- inputs and
+Outputs: tests/golden/{sumtree,replay_uniform,replay_per,replay_shapes,replay_horizon}.npz
+and the two checkpoints -- inputs and
 reference outputs only (data, no reference source).
 
     python tests/golden/gen_golden.py
@@ -247,21 +248,33 @@ def gen_shapes(m):
     """Non-scalar / non-default action and reward elements (crb:96-183, 530-548): sampled
     batches (np.random, rounds > 0), an explicit-index batch over indices whose n-step
     length broadcasts, and for case b one index whose length does not (numpy's error)."""
-    crb = m['circular_replay_buffer']
     out = {'cases': np.array([c[0] for c in SHAPE_CASES])}
-    rs = np.random.RandomState(21)
-    for name, C, n, stack, adds, gamma, B, rounds, (ash, adt), (rsh, rdt) in SHAPE_CASES:
+    _shape_cases(m, SHAPE_CASES, np.random.RandomState(21), out)
+    np.savez_compressed(os.path.join(OUT, 'replay_shapes.npz'), **out)
+
+
+def _shape_cases(m, cases, rs, out, prefix='', p_term=0.12, rewards=None, patterned=False):
+    """The cases of gen_shapes into ``out``; ``rewards(rs, shape, dtype)`` replaces the
+    default small-multiple rewards (the long-horizon cases need rewards whose sum depends on
+    the order of the additions)."""
+    crb = m['circular_replay_buffer']
+    for name, C, n, stack, adds, gamma, B, rounds, (ash, adt), (rsh, rdt) in cases:
         mem = crb.OutOfGraphReplayBuffer(observation_shape=(4, 4), stack_size=stack,
                                          replay_capacity=C, batch_size=B, update_horizon=n,
                                          gamma=gamma, action_shape=ash, action_dtype=np.dtype(adt),
                                          reward_shape=rsh, reward_dtype=np.dtype(rdt))
         obs = rs.randint(0, 256, (adds, 4, 4)).astype(np.uint8)
+        if patterned:    # frame i = the bytes 16i .. 16i + 15 (mod 256): a small file
+            obs = ((16 * np.arange(adds)[:, None, None] + np.arange(16).reshape(4, 4)) % 256).astype(np.uint8)
         act = rs.randint(-3, 100, (adds,) + ash).astype(adt)
-        rew = (rs.randint(-4, 5, (adds,) + rsh) * 0.37).astype(rdt)
-        term = (rs.rand(adds) < 0.12).astype(np.uint8)
+        if rewards is None:
+            rew = (rs.randint(-4, 5, (adds,) + rsh) * 0.37).astype(rdt)
+        else:
+            rew = rewards(rs, (adds,) + rsh, rdt)
+        term = (rs.rand(adds) < p_term).astype(np.uint8)
         for i in range(adds):
             mem.add(obs[i], act[i], rew[i], term[i])
-        pre = name + '_'
+        pre = prefix + name + '_'
         out[pre + 'meta'] = np.array([C, n, stack, adds, B, rounds], np.int64)
         out[pre + 'gamma'] = np.float64(gamma)
         out[pre + 'obs'], out[pre + 'act'], out[pre + 'rew'], out[pre + 'term'] = obs, act, rew, term
@@ -295,7 +308,176 @@ def gen_shapes(m):
             except ValueError as e:
                 out[pre + 'bad_error'] = np.array(str(e))
             out[pre + 'bad_index'] = np.int64(bad[0])
-    np.savez_compressed(os.path.join(OUT, 'replay_shapes.npz'), **out)
+
+
+# --------------------------------------------------------------------------
+# Long update horizons (replay_horizon.npz): np.sum(discount[:L] * rewards) (crb:540-541)
+# adds a contiguous 1-D array of 8 or more elements pairwise, not left to right, so the
+# n-step reward's last bits depend on the order from n = 8 on.  Rewards are randn float32
+# (the {-1, 0, 0.5, 1} set of gen_replay sums exactly in any order).
+# --------------------------------------------------------------------------
+HORIZONS = (7, 8, 9, 17, 64, 65, 137)
+HORIZON_STACKS = (1, 4)
+HORIZON_KEYS = ['state', 'action', 'reward', 'next_state', 'next_action', 'next_reward',
+                'terminal', 'indices']
+HORIZON_SNAP_KEYS = ['action', 'reward', 'next_action', 'next_reward', 'terminal', 'indices']
+
+# (name, capacity, n, stack, adds, gamma, B, rounds, action (shape, dtype), reward (shape, dtype))
+HORIZON_ELEM_CASES = [
+    ('f64_n9', 60, 9, 2, 171, 0.99, 16, 4, ((), 'int32'), ((), 'float64')),
+    ('f64_n17', 70, 17, 2, 190, 0.99, 16, 4, ((), 'int32'), ((), 'float64')),
+    ('f16_n9', 60, 9, 2, 171, 0.99, 16, 4, ((), 'int32'), ((), 'float16')),
+    ('f16_n17', 70, 17, 1, 190, 0.99, 16, 4, ((), 'int32'), ((), 'float16')),
+    ('i32_n9', 60, 9, 2, 171, 0.99, 16, 4, ((), 'int32'), ((), 'int32')),
+    ('i32_n17', 70, 17, 2, 190, 0.99, 16, 4, ((), 'int32'), ((), 'int32')),
+    ('shaped_n9', 60, 9, 2, 171, 0.99, 16, 4, ((), 'int32'), ((9,), 'float32')),
+]
+# the element cases whose stored reward can show the order of the additions: a float16 or
+# int32 reward is the float32 / float64 sum rounded to 11 bits / truncated to an integer,
+# which hides a last-bit difference, and a shaped reward is summed row by row (left to right)
+HORIZON_ELEM_ORDER_VISIBLE = ('f64_n9', 'f64_n17')
+
+
+def _horizon_rewards(rs, shape, dtype):
+  if np.dtype(dtype).kind == 'i':
+    return rs.randint(-1000, 1001, shape).astype(dtype)
+  return rs.randn(*shape).astype(dtype)
+
+
+def left_to_right_rewards(store_reward, store_terminal, discount, C, n, indices):
+  """The n-step rewards of ``indices`` with the products of crb:540-541 added LEFT TO RIGHT in
+  their own type (float32 for a float32 store, numpy's promotion otherwise) -- what the
+  goldens of a horizon >= 8 must differ from -- and each trajectory's length."""
+  out, lens = [], []
+  for idx in indices:
+    ring = [(int(idx) + j) % C for j in range(n)]
+    t = store_terminal[ring].astype(bool)
+    L = int(np.argmax(t)) + 1 if t.any() else n
+    prod = discount[:L] * store_reward[ring[:L]]
+    acc = prod.dtype.type(0)
+    for v in prod:
+      acc = prod.dtype.type(acc + v)
+    out.append(acc)
+    lens.append(L)
+  return np.array(out), np.array(lens)
+
+
+def gen_horizon(m):
+  """Uniform and prioritized buffers at update horizons 7 .. 137, stack 1 and 4, (2, 2) uint8
+  observations, capacity n + stack + 40: sampled rounds and an explicit-index batch as in
+  gen_replay, plus explicit batches over EVERY valid index at several points of the add
+  stream (``snap_*``, scalars only), so trajectories of every length, with a terminal at the
+  first step, at the last step and absent, wrapping the ring end, are recorded.  Then the
+  scalar-reward element cases (float64 / float16 / int32, n = 9 and 17) and one shaped (9,)
+  float32 reward, in gen_shapes style."""
+  crb = m['circular_replay_buffer']
+  prb = m['prioritized_replay_buffer']
+  out = {}
+  names = []
+  for prioritized in (False, True):
+    rs = np.random.RandomState(31 if prioritized else 37)
+    for n in HORIZONS:
+      for stack in HORIZON_STACKS:
+        name = '%s_n%d_s%d' % ('per' if prioritized else 'uni', n, stack)
+        names.append(name)
+        C, B, rounds, gamma = n + stack + 40, 8, 3, 0.99
+        adds = 3 * C + 7
+        # frame i holds the bytes 4i .. 4i + 3 (mod 256): every frame of a stack differs, and
+        # the file stays small
+        obs = ((4 * np.arange(adds)[:, None, None] + np.arange(4).reshape(2, 2)) % 256).astype(np.uint8)
+        # the terminals are re-drawn (same stream) until the case shows what it is for
+        for attempt in range(100):
+          act = rs.randint(0, 6, size=adds).astype(np.int32)
+          rew = rs.randn(adds).astype(np.float32)
+          term = (rs.rand(adds) < 1.0 / (3 * n + 60)).astype(np.uint8)
+          # two terminals placed so that, at the last snapshot, one trajectory ends at its
+          # first step and one at its n-th
+          term[adds - n - 16:adds] = 0
+          term[adds - n - 12] = 1
+          term[adds - 2] = 1
+          prio_in = (rs.randint(1, 41, size=adds) / 20.0).astype(np.float32)
+          cls = prb.OutOfGraphPrioritizedReplayBuffer if prioritized else crb.OutOfGraphReplayBuffer
+          mem = cls(observation_shape=(2, 2), stack_size=stack, replay_capacity=C, batch_size=B,
+                    update_horizon=n, gamma=gamma)
+          snaps = sorted(set([C + 3, C + C // 3, 2 * C - 5, 2 * C + 5, adds - 9, adds]))
+          keys = HORIZON_KEYS + (['probs'] if prioritized else [])
+          snap_rows = {k: [] for k in HORIZON_SNAP_KEYS}
+          snap_len, l2r, lens = [], [], []
+          for i in range(adds):
+            if prioritized:
+              mem.add(obs[i], act[i], rew[i], term[i], prio_in[i])
+            else:
+              mem.add(obs[i], act[i], rew[i], term[i])
+            if i + 1 in snaps:
+              valid = [j for j in range(C) if mem.is_valid_transition(j)]
+              batch = mem.sample_transition_batch(batch_size=len(valid), indices=valid)
+              for k, v in zip(keys, batch):
+                if k in snap_rows:
+                  snap_rows[k].append(np.array(v))
+              snap_len.append(len(valid))
+              a, b = left_to_right_rewards(mem._store['reward'], mem._store['terminal'],
+                                           mem._cumulative_discount_vector, C, n, valid)
+              l2r.append(a)
+              lens.append(b)
+          pre = name + '_'
+          seed = 977 + C
+          out[pre + 'meta'] = np.array([C, n, stack, adds, B, rounds, int(mem.add_count), seed],
+                                       np.int64)
+          out[pre + 'obs'], out[pre + 'act'], out[pre + 'rew'], out[pre + 'term'] = obs, act, rew, term
+          if prioritized:
+            out[pre + 'prio_in'] = prio_in
+          out[pre + 'snaps'] = np.array([snaps, snap_len], np.int64)   # add counts, batch sizes
+          for k in HORIZON_SNAP_KEYS:
+            out[pre + 'snap_' + k] = np.concatenate(snap_rows[k])
+          random.seed(seed) if prioritized else np.random.seed(seed)
+          rows = {k: [] for k in keys}
+          for _ in range(rounds):
+            for k, v in zip(keys, mem.sample_transition_batch()):
+              rows[k].append(np.array(v))
+          for k in keys:
+            out[pre + k] = np.stack(rows[k])
+          fixed = [i for i in range(C) if mem.is_valid_transition(i)][:5]
+          for k, v in zip(keys, mem.sample_transition_batch(batch_size=len(fixed), indices=fixed)):
+            out[pre + 'fixed_' + k] = np.array(v)
+          # what the fixture must be able to show
+          got, l2r, lens = out[pre + 'snap_reward'], np.concatenate(l2r), np.concatenate(lens)
+          terms = out[pre + 'snap_terminal'].astype(bool)
+          assert got.dtype == np.float32 and l2r.dtype == np.float32
+          differ = float(np.mean(got != l2r))
+          print('%-14s C %3d  %4d trajectories  L %3d..%3d  no terminal %.2f  differ from '
+                'left-to-right %.3f' % (name, C, len(got), lens.min(), lens.max(),
+                                        np.mean(~terms), differ))
+          assert n >= 8 or differ == 0.0, (name, differ)
+          if ((n < 8 or differ >= 0.25) and (terms & (lens == 1)).any() and
+              (terms & (lens == n)).any() and np.mean(~terms) >= 0.3 and
+              len(set(lens.tolist())) >= min(n, 12)):
+            break
+        else:
+          raise AssertionError(name)
+  out['cases'] = np.array(names)
+  out['gamma'] = np.float64(0.99)
+  out['elem_cases'] = np.array([c[0] for c in HORIZON_ELEM_CASES])
+  _shape_cases(m, HORIZON_ELEM_CASES, np.random.RandomState(41), out, prefix='elem_',
+               p_term=0.02, rewards=_horizon_rewards, patterned=True)
+  for name, C, n, stack, adds, gamma, B, rounds, _, (rsh, rdt) in HORIZON_ELEM_CASES:
+    pre = 'elem_' + name + '_'
+    # the store after the adds, as the reference pads it (crb:234-260)
+    mem = crb.OutOfGraphReplayBuffer(observation_shape=(4, 4), stack_size=stack,
+                                     replay_capacity=C, batch_size=B, update_horizon=n,
+                                     gamma=gamma, reward_shape=rsh, reward_dtype=np.dtype(rdt))
+    for i in range(adds):
+      mem.add(out[pre + 'obs'][i], out[pre + 'act'][i], out[pre + 'rew'][i], out[pre + 'term'][i])
+    if rsh:
+      continue
+    idx = np.concatenate([out[pre + 'indices'].reshape(-1), out[pre + 'fixed_indices']])
+    got = np.concatenate([out[pre + 'reward'].reshape(-1), out[pre + 'fixed_reward']])
+    l2r, _ = left_to_right_rewards(mem._store['reward'], mem._store['terminal'],
+                                   mem._cumulative_discount_vector, C, n, idx)
+    differ = float(np.mean(got != l2r.astype(rdt)))
+    print('elem_%-10s %3d rewards  differ from left-to-right %.3f' % (name, len(got), differ))
+    if name in HORIZON_ELEM_ORDER_VISIBLE:
+      assert l2r.dtype == np.float64 and differ >= 0.25, (name, differ)
+  np.savez_compressed(os.path.join(OUT, 'replay_horizon.npz'), **out)
 
 
 if __name__ == '__main__':
@@ -306,12 +488,16 @@ if __name__ == '__main__':
   if sys.argv[1:] == ['shapes']:
     gen_shapes(mods)
     sys.exit(0)
+  if sys.argv[1:] == ['horizon']:
+    gen_horizon(mods)
+    sys.exit(0)
   gen_sumtree(mods)
   gen_replay(mods, prioritized=False)
   gen_replay(mods, prioritized=True)
   gen_checkpoint(mods)
   gen_checkpoint_per(mods)
   gen_shapes(mods)
+  gen_horizon(mods)
   for f in sorted(os.listdir(OUT)):
     if f.endswith('.npz'):
       print(f, os.path.getsize(os.path.join(OUT, f)))
