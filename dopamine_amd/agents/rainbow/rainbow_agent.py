@@ -167,6 +167,14 @@ class RainbowAgent(dqn_agent.DQNAgent):
   # the one-kernel loss, so off by default.
   split_c51 = False
 
+  # the fused loss kernels (dq_c51_loss_fused / _online) keep one atom per lane of one wave
+  FUSED_MAX_ATOMS = 64
+
+  def _fused(self):
+    """Above 64 atoms the Nature-CNN agent takes fused_head=False's schedule -- stored
+    logits, then dq_c51_loss (its wide kernel) -- bitwise an agent constructed that way."""
+    return self._num_atoms <= self.FUSED_MAX_ATOMS and super()._fused()
+
   def _head_from(self):
     if self._fused() and self.split_c51 and self.num_actions <= 16 and self._num_atoms <= 64:
       return 8

@@ -1,7 +1,7 @@
 // C51 device pieces shared by learner.hip (the loss kernels) and nature_cnn.hip (the
-// target half riding in the fused forward): logit sources, DPP wave reductions, and the
-// target half of rainbow_agent.py:200-251 + 340-494 (target softmax / Q / greedy action /
-// Eq.-7 projection) as a per-sample block body.
+// target half riding in the fused forward): logit sources, DPP wave reductions, the chunked
+// rows of supports wider than a wave, and the target half of rainbow_agent.py:200-251 +
+// 340-494 (target softmax / Q / greedy action / Eq.-7 projection) as a per-sample block body.
 #pragma once
 #include "common.h"
 
@@ -101,6 +101,59 @@ __device__ __forceinline__ float fast_min(float v) {
   v = fminf(v, dpp_ror<0x122>(v));
   v = fminf(v, dpp_ror<0x121>(v));
   return fminf(fminf(rl(v, 0), rl(v, 16)), fminf(rl(v, 32), rl(v, 48)));
+}
+
+// Rows wider than a wave (k_c51_wide, 65..256 atoms): a lane holds atoms lane + 64 c,
+// c < kC51WideChunks, in registers, and a row-wide reduction is fast_max / fast_sum of each
+// chunk combined in chunk order -- one wave, no LDS, no barrier, one fixed order.  nch =
+// ceil(N / 64) is wave-uniform; chunk 0 is always there.
+constexpr int kC51WideChunks = 4;
+struct WideRow {
+  float v[kC51WideChunks];
+};
+// row[lane + 64 c] (clamped loads, all in flight together), `fill` past the row's end
+__device__ __forceinline__ WideRow wide_load(const float* row, int N, int lane, float fill) {
+  WideRow r;
+#pragma unroll
+  for (int c = 0; c < kC51WideChunks; ++c) {
+    const int i = lane + c * kWave;
+    const float x = row[min(i, N - 1)];
+    r.v[c] = i < N ? x : fill;
+  }
+  return r;
+}
+__device__ __forceinline__ float wide_max(const WideRow& r, int nch) {
+  float m = fast_max(r.v[0]);
+#pragma unroll
+  for (int c = 1; c < kC51WideChunks; ++c)
+    if (c < nch) m = fmaxf(m, fast_max(r.v[c]));
+  return m;
+}
+__device__ __forceinline__ float wide_sum(const WideRow& r, int nch) {
+  float s = fast_sum(r.v[0]);
+#pragma unroll
+  for (int c = 1; c < kC51WideChunks; ++c)
+    if (c < nch) s = __fadd_rn(s, fast_sum(r.v[c]));
+  return s;
+}
+// The softmax's pieces of a row whose lanes past the end hold -inf: sh = x - max(x) and
+// e = exp(sh) (both 0 past the end); returns sum(e).  k_c51's operations, chunk by chunk.
+__device__ __forceinline__ float wide_softmax_terms(const WideRow& x, int N, int nch, int lane,
+                                                    WideRow& sh, WideRow& e) {
+  const float mx = wide_max(x, nch);
+#pragma unroll
+  for (int c = 0; c < kC51WideChunks; ++c) {
+    const bool on = lane + c * kWave < N;
+    sh.v[c] = on ? __fsub_rn(x.v[c], mx) : 0.0f;
+    e.v[c] = on ? expf(sh.v[c]) : 0.0f;
+  }
+  return wide_sum(e, nch);
+}
+// The Eq.-7 clipped quotient c(i, j) = clip(1 - |clip(Tz_j) - z_i| / dz, 0, 1) of k_c51 and
+// c51_target_block, for a kernel that forms it on the fly instead of keeping the table
+__device__ __forceinline__ float c51_quot(float tzj, float zi, float dz) {
+  const float c = __fsub_rn(1.0f, __fdiv_rn(fabsf(__fsub_rn(tzj, zi)), dz));
+  return fminf(fmaxf(c, 0.0f), 1.0f);
 }
 
 // The fused d h's dot product for column `col` of LDS-resident W2 rows (row stride `ld`):

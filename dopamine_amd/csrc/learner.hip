@@ -424,6 +424,145 @@ static size_t c51_lds(int A, int N, int H, int nw) {
   return (size_t)c51_head_floats(A, N, nw) * sizeof(float) + (H ? c51_w2_lds_bytes(N, H) : 0);
 }
 
+// ---------------------------------------------------------------------------
+// C51 on 65..256 atoms (stored logits only): k_c51's contract with a row spread over four
+// 64-atom chunks.  One 256-thread block per sample b.
+//   before the barrier  wave w takes whole target rows w, w + 4, ..: a lane holds atoms
+//                       lane + 64 c (c51_dev.h WideRow), so a row's max, softmax sum and Q
+//                       reduce inside the wave, chunk by chunk in chunk order.  The last wave
+//                       (the one with the fewest rows) also takes the chosen online row and
+//                       leaves sh_i = y_i - max y, p_i and log sum exp(sh) in LDS.  Thread j
+//                       forms clip(Tz_j); every thread zeroes its share of the rows not
+//                       chosen and folds its share of all B replay probabilities.
+//   after it            thread i < N is target atom i: it takes the greedy row (first max of
+//                       Q) and sums c(i, j) p_j in j order, c(i, j) formed on the fly from
+//                       clip(Tz_j) -- the N x N table k_c51 keeps is 256 KB at N = 256.
+//                       The loss terms are summed per wave and the four partials in wave
+//                       order, after a second barrier.
+// Every reduction has one fixed order, nothing is accumulated atomically and nothing lives
+// outside the block: two launches on the same inputs are bitwise equal.
+// ---------------------------------------------------------------------------
+constexpr int kC51WideT = 256, kC51WideWaves = kC51WideT / kWave;
+constexpr int kC51WideMaxAtoms = kC51WideChunks * kWave;
+static_assert(kC51WideMaxAtoms == kC51WideT, "one thread per target atom");
+
+// dynamic LDS floats: [A][N] target probabilities, [A] target Q, [N] clip(Tz), [N] sh,
+// [N] online p, 4 loss partials + 4 probability minima + lse
+__host__ __device__ constexpr int c51_wide_floats(int A, int N) { return A * N + A + 3 * N + 12; }
+
+template <bool kProbs>
+__global__ __launch_bounds__(kC51WideT) void k_c51_wide(C51Args a) {
+  warm_kernargs<sizeof(C51Args)>();
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int N = a.N, A = a.A, b = blockIdx.x, t = threadIdx.x;
+  const int lane = t & 63, wave = t >> 6, nch = (N + kWave - 1) >> 6;
+  float* s_p = smem;                 // [A][N] target probabilities
+  float* s_q = s_p + A * N;          // [A]    target Q
+  float* s_tz = s_q + A;             // [N]    clip(Tz_j)
+  float* s_sh = s_tz + N;            // [N]    chosen online row, y_i - max y
+  float* s_py = s_sh + N;            // [N]    chosen online row, softmax
+  float* s_red = s_py + N;           // [0..3] loss partials, [4..7] min probs, [8] lse
+  const bool on = t < N;
+  const float ninf = -__builtin_inff();
+  const float z = a.support[min(t, N - 1)];
+  const int ab = a.act[b];
+  const float rew_b = a.rew[b], term_b = (float)a.term[b];
+  const float vmin = a.support[0], vmax = a.support[N - 1], z1 = a.support[1];
+  const float pr_b = kProbs ? a.probs[b] : 0.0f;
+  const float dz = __fsub_rn(z1, vmin);
+  {
+    const float gt = __fmul_rn(a.cg, __fsub_rn(1.0f, term_b));
+    if (on) s_tz[t] = fminf(fmaxf(__fadd_rn(rew_b, __fmul_rn(gt, z)), vmin), vmax);
+  }
+  if (kProbs) {   // PER: the minimum over all B probabilities (k_c51's weight, rb:277-280)
+    float pm = a.probs[min(t, a.B - 1)];
+    for (int i = t + kC51WideT; i < a.B; i += kC51WideT) pm = fminf(pm, a.probs[i]);
+    pm = fast_min(pm);
+    if (lane == 0) s_red[4 + wave] = pm;
+  }
+  WideRow zc;       // the support at this lane's atoms
+#pragma unroll
+  for (int c = 0; c < kC51WideChunks; ++c) zc.v[c] = a.support[min(lane + c * kWave, N - 1)];
+  for (int act = wave; act < A; act += kC51WideWaves) {
+    const WideRow x = wide_load(a.tl + ((int64_t)b * A + act) * N, N, lane, ninf);
+    WideRow sh, e, zp;
+    const float s = wide_softmax_terms(x, N, nch, lane, sh, e);
+#pragma unroll
+    for (int c = 0; c < kC51WideChunks; ++c) {
+      const int i = lane + c * kWave;
+      const float p = __fdiv_rn(e.v[c], s);
+      zp.v[c] = i < N ? __fmul_rn(zc.v[c], p) : 0.0f;
+      if (i < N) s_p[act * N + i] = p;
+    }
+    const float q = wide_sum(zp, nch);
+    if (lane == 0) s_q[act] = q;
+  }
+  if (wave == kC51WideWaves - 1) {
+    const WideRow y = wide_load(a.ol + ((int64_t)b * A + ab) * N, N, lane, ninf);
+    WideRow sh, ey;
+    const float sy = wide_softmax_terms(y, N, nch, lane, sh, ey);
+#pragma unroll
+    for (int c = 0; c < kC51WideChunks; ++c) {
+      const int i = lane + c * kWave;
+      if (i < N) {
+        s_sh[i] = sh.v[c];
+        s_py[i] = __fdiv_rn(ey.v[c], sy);
+      }
+    }
+    if (lane == 0) s_red[8] = logf(sy);
+  }
+  // grad_logits is fully written: zeros on the rows not chosen
+  {
+    float* g = a.grad + (int64_t)b * A * N;
+    for (int act = 0; act < A; ++act)
+      if (act != ab && on) g[act * N + t] = 0.0f;
+  }
+  __syncthreads();   // s_p, s_q, s_tz, s_sh, s_py, s_red[4..8] complete
+  float w = 1.0f;
+  if (kProbs) {
+    const float pm = fminf(fminf(s_red[4], s_red[5]), fminf(s_red[6], s_red[7]));
+    const float m = __fdiv_rn(1.0f, sqrt_rn(__fadd_rn(pm, 1e-10f)));
+    w = __fdiv_rn(__fdiv_rn(1.0f, sqrt_rn(__fadd_rn(pr_b, 1e-10f))), m);
+  }
+  const float gscale = __fmul_rn(w, __fdiv_rn(1.0f, (float)a.B));
+  int astar = 0;     // greedy target action, first max
+  {
+    float best = s_q[0];
+    for (int act = 1; act < A; ++act) {
+      const float qa = s_q[act];
+      if (qa > best) {
+        best = qa;
+        astar = act;
+      }
+    }
+  }
+  const float* pst = s_p + astar * N;
+  float term = 0.0f;
+  if (on) {
+    float proj = 0.0f;               // sum_j c(i, j) p_j in j order (rb:340-494)
+    int j = 0;
+    for (; j + 8 <= N; j += 8) {     // 8 terms' LDS reads in flight, then summed in order
+      float tt[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) tt[u] = __fmul_rn(c51_quot(s_tz[j + u], z, dz), pst[j + u]);
+#pragma unroll
+      for (int u = 0; u < 8; ++u) proj = __fadd_rn(proj, tt[u]);
+    }
+    for (; j < N; ++j) proj = __fadd_rn(proj, __fmul_rn(c51_quot(s_tz[j], z, dz), pst[j]));
+    term = __fmul_rn(proj, __fsub_rn(s_red[8], s_sh[t]));
+    a.grad[((int64_t)b * A + ab) * N + t] = __fmul_rn(gscale, __fsub_rn(s_py[t], proj));
+  }
+  const float part = fast_sum(term);
+  if (!a.loss_out && !a.prio_out) return;
+  if (lane == 0) s_red[wave] = part;
+  __syncthreads();
+  if (t == 0) {
+    const float loss = __fadd_rn(__fadd_rn(__fadd_rn(s_red[0], s_red[1]), s_red[2]), s_red[3]);
+    if (a.loss_out) a.loss_out[b] = loss;
+    if (a.prio_out) a.prio_out[b] = sqrt_rn(__fadd_rn(loss, 1e-10f));
+  }
+}
+
 // mean(w * loss) for summaries (rb:298-301); launched only when requested.
 __global__ __launch_bounds__(64) void k_wmean(const float* loss, const float* probs, int B,
                                               float* out) {
@@ -728,20 +867,27 @@ int dq_c51_loss(const float* online_logits, const float* target_logits, const in
   DQ_CHECK_ARG(online_logits && target_logits && actions && rewards && terminals && support &&
                    grad_logits,
                "null argument");
-  DQ_CHECK_ARG(num_atoms >= 2 && num_atoms <= 64, "num_atoms must be in [2, 64]");
+  DQ_CHECK_ARG(num_atoms >= 2 && num_atoms <= kC51WideMaxAtoms, "num_atoms must be in [2, 256]");
   DQ_CHECK_ARG(batch >= 1 && num_actions >= 1 && num_actions <= 256, "bad batch / num_actions");
   C51Args a{online_logits, target_logits, actions, rewards, terminals, probs, support,
             batch, num_actions, num_atoms, cumulative_gamma, grad_logits, loss_out,
             priorities_out, mean_loss_out};
   DQ_CHECK_ARG(!mean_loss_out || loss_out, "mean_loss_out needs loss_out");
   DQ_CHECK_ARG(num_actions <= 64, "num_actions must be <= 64");
-  const int waves = num_actions < 16 ? num_actions : 16;
-  const size_t shm = c51_lds(num_actions, num_atoms, 0, waves);
-  auto kern = probs ? k_c51<LogitsDirect, kC51Probs> : k_c51<LogitsDirect, 0>;
-  hipLaunchKernelGGL(kern, dim3(batch), dim3(64 * waves), shm, (hipStream_t)stream,
-                     a, LogitsDirect{online_logits, num_actions * num_atoms},
-                     LogitsDirect{target_logits, num_actions * num_atoms}, C51Extra{});
-  DQ_CHECK_LAUNCH("k_c51");
+  if (num_atoms > kWave) {   // a row wider than a wave: the chunked kernel
+    const size_t shm = (size_t)c51_wide_floats(num_actions, num_atoms) * sizeof(float);
+    auto kern = probs ? k_c51_wide<true> : k_c51_wide<false>;
+    hipLaunchKernelGGL(kern, dim3(batch), dim3(kC51WideT), shm, (hipStream_t)stream, a);
+    DQ_CHECK_LAUNCH("k_c51_wide");
+  } else {
+    const int waves = num_actions < 16 ? num_actions : 16;
+    const size_t shm = c51_lds(num_actions, num_atoms, 0, waves);
+    auto kern = probs ? k_c51<LogitsDirect, kC51Probs> : k_c51<LogitsDirect, 0>;
+    hipLaunchKernelGGL(kern, dim3(batch), dim3(64 * waves), shm, (hipStream_t)stream,
+                       a, LogitsDirect{online_logits, num_actions * num_atoms},
+                       LogitsDirect{target_logits, num_actions * num_atoms}, C51Extra{});
+    DQ_CHECK_LAUNCH("k_c51");
+  }
   if (mean_loss_out) {
     hipLaunchKernelGGL(k_wmean, dim3(1), dim3(64), 0, (hipStream_t)stream, loss_out, probs, batch,
                        mean_loss_out);

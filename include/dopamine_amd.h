@@ -252,7 +252,12 @@ int dq_rider_chain(const dq_rider* first, const dq_rider* second, dq_rider* out)
  * rainbow_agent.py:340-494).  Logits (B, A, N) float32.  grad_logits (B,A,N) is
  * fully written: d mean(w * loss) / d online_logits (TF CE backprop
  * softmax - labels).  probs NULL => replay_scheme 'uniform' (weights 1).
- * loss_out/priorities_out (B,), mean_loss_out (1,): may be NULL. */
+ * loss_out/priorities_out (B,), mean_loss_out (1,): may be NULL.
+ * Limits: 2 <= num_atoms <= 256, num_actions <= 64, any batch (the PER weight's minimum
+ * runs over all B probabilities).  Up to 64 atoms a row is one wave; 65..256 atoms run a
+ * kernel of their own (four 64-atom chunks per row), with the same contract and the same
+ * fixed-order reductions: two calls on the same inputs are bitwise equal.  Anything else is
+ * DQ_E_ARG before a launch. */
 int dq_c51_loss(const float* online_logits, const float* target_logits, const int32_t* actions,
                 const float* rewards, const uint8_t* terminals, const float* probs,
                 const float* support, int32_t batch, int32_t num_actions, int32_t num_atoms,
