@@ -20,6 +20,7 @@ from dopamine_amd import _lib
 from dopamine_amd import ops
 from dopamine_amd import parallel
 from dopamine_amd.agents import networks
+from dopamine_amd.agents.dqn import data_parallel
 from dopamine_amd.agents.optimizers import RMSPropOptimizer
 from dopamine_amd.replay_memory import circular_replay_buffer
 
@@ -133,16 +134,14 @@ class DQNAgent(object):
     # torch.distributed's collectives (each forked onto the process group's own stream)
     self.native_comm = bool(native_comm)
     # N > 1: 'collective' -- the gradient buckets' all-reduce (RCCL / gloo) on a second stream
-    # beside the backward (_split_step); 'peer' -- the exchange over peer memory inside the
-    # backward's own launches on ONE stream (parallel.PeerExchange): one node,
+    # beside the backward (data_parallel.Exchange); 'peer' -- the exchange over peer memory inside
+    # the backward's own launches on ONE stream (parallel.PeerExchange): one node,
     # the HIP Nature CNN with the fused Rainbow schedule and TF1 Adam
     if exchange not in ('collective', 'peer'):
       raise ValueError("exchange must be 'collective' or 'peer'")
     self.exchange = exchange
     self._peer = None
-    self._rccl = None
-    self._pg_conv = None           # a second communicator for the conv bucket (see _split_step)
-    self._fc_pending = None        # event: the previous step's fc all-reduce + update are done
+    self._dp = None                # N > 1: the collective exchange (data_parallel.Exchange)
     self._defer_fc = False         # set by train_gradient_steps (learner-only loop)
     self.use_hip_graph = use_hip_graph
     self.pipeline = pipeline
@@ -187,35 +186,29 @@ class DQNAgent(object):
       self._opt = self.optimizer.build(self.online_convnet.fp.flat,
                                        segments=self.online_convnet.fp.segments())
       self._side = torch.cuda.Stream(self._device, priority=self.side_priority)
-      # N > 1: the fc bucket's all-reduces (comm_priority -1: a high-priority queue, whose
-      # workgroups are dispatched ahead of the main queue's pending ones)
-      self._comm = torch.cuda.Stream(self._device, priority=self.comm_priority)
-      self._comm_opt = torch.cuda.Stream(self._device)    # ... and the Adam parts behind them
       if self._pg is not None:
-        self._broadcast_replica()
+        # collective, in this order on every rank: the replica's broadcast (Exchange's
+        # constructor), the peer exchange, the native communicators
+        self._dp = data_parallel.Exchange(
+            self._pg, self._device, self.online_convnet.fp, self._opt, self._replica_tensors(),
+            shard_optimizer=self.shard_optimizer, comm_priority=self.comm_priority)
         if self.exchange == 'peer':
           self._peer = self._make_peer_exchange()
-        self._rccl = self._make_native_comms()
+        self._dp.make_native_comms(self.native_comm, self._split_allreduce())
     self._observation = None
     self._last_observation = None
     self.last_loss = None
 
+  def _opt_tensors(self):
+    """(attribute name, tensor) of the optimizer's tensors other than the parameters, by name."""
+    for k, v in sorted(vars(self._opt).items()):
+      if isinstance(v, torch.Tensor) and v.data_ptr() != self.online_convnet.fp.flat.data_ptr():
+        yield k, v
+
   def _replica_tensors(self):
     """Everything a replica's updates depend on: parameters and optimizer state."""
-    ts = [self.online_convnet.fp.flat, self.target_convnet.fp.flat]
-    ts += [v for k, v in sorted(vars(self._opt).items())
-           if isinstance(v, torch.Tensor) and v.data_ptr() != self.online_convnet.fp.flat.data_ptr()]
-    return ts
-
-  def _make_native_comms(self):
-    """(fc bucket, conv bucket) RcclComm pair for the split schedule over RCCL, or None
-    (gloo, or a schedule without buckets).  Collective: every rank constructs its agent."""
-    import torch.distributed as dist
-    if not (self.native_comm and self._split_allreduce() and dist.get_backend(self._pg) == 'nccl'):
-      return None
-    if not parallel.native_comm_available(self._pg, self._device):
-      return None        # every rank agreed: torch.distributed's collectives instead
-    return (parallel.RcclComm(self._pg, self._device), parallel.RcclComm(self._pg, self._device))
+    return ([self.online_convnet.fp.flat, self.target_convnet.fp.flat] +
+            [v for _, v in self._opt_tensors()])
 
   def _make_peer_exchange(self):
     """The peer-memory exchange (exchange='peer').  Collective: every rank constructs its
@@ -232,7 +225,7 @@ class DQNAgent(object):
       # a head of fc1 floats would join the replicated conv bucket, which the peers read in
       # the exchange launch after this learner may have rewritten it (dq_cnn_backward_peer)
       raise ValueError("exchange='peer': the fc bucket does not split into %d equal 16-byte "
-                       'slices (networks.FC_BUCKET_ALIGN)' % self._world())
+                       'slices (networks.FC_BUCKET_ALIGN)' % self._dp.world)
     return parallel.PeerExchange(self._pg, self._device, self.online_convnet.fp.grad,
                                  self.online_convnet.fp.flat, lo, n)
 
@@ -251,47 +244,27 @@ class DQNAgent(object):
     launches still read."""
     self._join_fc()
     torch.cuda.synchronize(self._device)
+    if self._peer is None and self._rccl is None:
+      return
     if self._peer is not None:
-      import torch.distributed as dist
-      dist.barrier(group=self._pg)
-      self._graph_sets = {}
-      self._graph_pool = None
+      self._dp.barrier()
+    self._graph_sets = {}
+    self._graph_pool = None
+    if self._peer is not None:
       self._peer.close()
       self._peer = None
-      self._closed = True
-    if self._rccl is not None:
-      self._graph_sets = {}
-      self._graph_pool = None
-      parallel.forget_capture_probes(self._rccl)
-      for c in self._rccl:
-        c.destroy()
-      self._rccl = None
-      self._closed = True
+    self._dp.destroy()
+    self._closed = True
 
   _closed = False
 
-  def _ar_fc(self, t):
-    """The fc bucket's all-reduce (mean), on the current (comm) stream."""
-    if self._rccl is not None:
-      return self._rccl[0].allreduce_mean_(t)
-    return parallel.allreduce_mean_(t, self._pg)
+  # the collective exchange's state under the names it had on the agent
+  _rccl = property(lambda self: None if self._dp is None else self._dp.rccl)
+  _pg_conv = property(lambda self: None if self._dp is None else self._dp.pg_conv)
 
-  def _ar_conv(self, t, second):
-    """The conv bucket's all-reduce (mean), on the current (main) stream: over the second
-    communicator when the fc bucket's may still be in flight on the first."""
-    if self._rccl is not None:
-      return self._rccl[1].allreduce_mean_(t)
-    return parallel.allreduce_mean_(t, self._conv_group() if second else self._pg)
-
-  def _broadcast_replica(self):
-    """Data-parallel replicas start from group rank 0's networks and optimizer state
-    (whatever seed each rank was built with), so the identical all-reduced updates
-    keep them bit-identical (parallel.replicas_in_sync)."""
-    import torch.distributed as dist
-    src = dist.get_process_group_ranks(self._pg)[0]
-    for t in self._replica_tensors():
-      dist.broadcast(t, src=src, group=self._pg)
-    torch.cuda.synchronize(self._device)
+  def _join_fc(self):
+    if self._dp is not None:
+      self._dp.join_fc()
 
   # ---------------------------------------------------------------- tracing
   # Parity tests compare every step of the bench path (graph replays, chunks) with a
@@ -448,17 +421,25 @@ class DQNAgent(object):
     parameters and optimizer state are bitwise the same either way."""
     return bool(self.keep_gradients or self._trace is not None)
 
-  def _backward(self, y, g, k=0):
-    if self._peer is not None:      # the exchange inside the backward (non-pipelined steps too)
-      self._hip['online'].backward_peer(g, self._opt, k, self._peer.desc)
+  def _hip_backward(self, g, k, groups=None, riders=None, head=None):
+    """Launches ``groups`` (None: all) of the HIP CNN's backward on d loss / d output g, step
+    parity k, with the riders and the target head that ride in them.  The peer exchange runs
+    inside the launches (non-pipelined steps too); otherwise the optimizer does where it is
+    fused (_fused_opt).  cnn.backward reads slot and store_grads with ``adam`` only, and
+    head_from only in a launch that carries a head."""
+    net = self._hip['online']
+    if self._peer is not None:
+      net.backward_peer(g, self._opt, k, self._peer.desc, riders=riders, head=head,
+                        defer_ag=riders is not None and self._peer_defer_ag)
       return
+    net.store_grads = self._store_grads()
+    net.backward(g, adam=self._opt if self._fused_opt() else None, slot=k, groups=groups,
+                 riders=riders, head=head,
+                 head_from=3 if head is None else self._bwd_head_from())
+
+  def _backward(self, y, g, k=0):
     if self._hip is not None:       # all gradients stored into the flat buffer
-      groups = (1, 7) if self._fused() else None    # fused: d h came with the loss
-      if self._fused_opt():
-        self._hip['online'].store_grads = self._store_grads()
-        self._hip['online'].backward(g, adam=self._opt, slot=k, groups=groups)
-      else:
-        self._hip['online'].backward(g, groups=groups)
+      self._hip_backward(g, k, (1, 7) if self._fused() else None)   # fused: d h came with the loss
       return
     if self._mlp is not None:       # likewise, by the MLP executor's L + 1 launches
       self._mlp['online'].backward(g)
@@ -609,9 +590,8 @@ class DQNAgent(object):
 
   def _peer_ready(self):
     if self._peer is not None and not self._peer_synced:
-      import torch.distributed as dist
       torch.cuda.synchronize(self._device)
-      dist.barrier(group=self._pg)
+      self._dp.barrier()
       self._peer_synced = True
 
   def _peer_flush(self):
@@ -688,8 +668,7 @@ class DQNAgent(object):
     for k, v in tg.items():
       self._ptgt[i][k].copy_(v)
 
-  def _grad_step(self, c, k=0, pipe=None):
-    pipe = self.pipeline if pipe is None else pipe
+  def _grad_step(self, c, k, pipe):
     if not pipe:
       self._prefetch(c)
     if self._rides():
@@ -698,55 +677,64 @@ class DQNAgent(object):
       self._forward_pair(c)
     y, g = self._loss(self._pbuf[c], c)
     if pipe and self._rides():
-      self._head = None
-      with self._replay.memory.recording() as riders:
-        self._post_loss(self._pbuf[c])
-        self._prefetch(1 - c)
-      riders = self._place_riders(riders)
-      if self._peer is not None:      # the exchange inside the backward's launches (one stream)
-        self._hip['online'].backward_peer(g, self._opt, k, self._peer.desc, riders=riders,
-                                          head=self._head, defer_ag=self._peer_defer_ag)
-        self._head = None
-        return
-      adam = self._opt if self._fused_opt() else None
-      f = self._bwd_first()
-      self._hip['online'].store_grads = self._store_grads()
-      self._hip['online'].backward(g, riders=riders, adam=adam, slot=k, head=self._head,
-                                   groups=(f, 7), head_from=self._bwd_head_from())
-      self._head = None
-    elif pipe:
-      main = torch.cuda.current_stream(self._device)
-      ev = torch.cuda.Event()
-      ev.record(main)
-      self._side.wait_event(ev)
-      with torch.cuda.stream(self._side):
-        self._post_loss(self._pbuf[c])
-        self._prefetch(1 - c)
-      self._backward(y, g, k)
-      main.wait_stream(self._side)
+      riders, head = self._record_riders(c)
+      self._hip_backward(g, k, (self._bwd_first(), 7), riders, head)
     else:
-      self._post_loss(self._pbuf[c])
-      self._backward(y, g, k)
+      self._beside_prefetch(c, pipe, lambda: self._backward(y, g, k))
 
-  # Data-parallel learners (N > 1) with the HIP CNN: the gradient all-reduce is
-  # bucketed and overlapped.  The backward's first _SPLIT grouped launches leave
-  # fc1/fc2's gradients final (93% of the 17.1 MB); their all-reduce runs on a
-  # comm stream while the prefetch branch and the remaining launches run, then
-  # the conv bucket is all-reduced and the optimizer applied.  Three graphs per
-  # step parity: head | tail | optimizer, the collectives between them.
+  def _record_riders(self, c):
+    """Step slot c's priority write-back and the next batch's sample and gather, recorded as
+    riders of the backward's launches -> (the riders placed, the target head on that batch)."""
+    self._head = None
+    with self._replay.memory.recording() as riders:
+      self._post_loss(self._pbuf[c])
+      self._prefetch(1 - c)
+    head, self._head = self._head, None
+    return self._place_riders(riders), head
+
+  def _beside_prefetch(self, c, pipe, backward):
+    """backward() after step slot c's _post_loss; pipelined, that and the next batch's
+    prefetch run on the side stream beside it."""
+    if not pipe:
+      self._post_loss(self._pbuf[c])
+      backward()
+      return
+    main = torch.cuda.current_stream(self._device)
+    ev = torch.cuda.Event()
+    ev.record(main)
+    self._side.wait_event(ev)
+    with torch.cuda.stream(self._side):
+      self._post_loss(self._pbuf[c])
+      self._prefetch(1 - c)
+    backward()
+    main.wait_stream(self._side)
+
+  # Data-parallel learners (N > 1) with the HIP CNN (data_parallel.Exchange.split_step): the
+  # backward's first _SPLIT grouped launches (the head) leave fc1/fc2's gradients final for
+  # their all-reduce beside the rest (the tail).  Three graphs per step parity: head | tail |
+  # optimizer, the collectives between them; the fused Rainbow path's head splits once more
+  # before fc1's forward, so the previous step's fc exchange may still run under the convs.
   _SPLIT = 3
 
   def _split_allreduce(self):
     return self._collective() and self._hip is not None and not self._fused_opt()
 
-  def _head_splits(self):
-    """The N > 1 head graph splits before fc1's forward (fused Rainbow path), so the
-    previous step's fc all-reduce + update may still run under the conv launches."""
-    return self._fused() and self._rides()
+  def _split_parts(self, c, k, pipe):
+    """(head_a | None, head_b, tail, opt): the callables of step slot c, parity k, that
+    Exchange.split_step issues (each alone is what one of the step's graphs captures)."""
+    tail = lambda: self._grad_step_tail(c, k, pipe)
+    opt = lambda: self._device_opt_step(k)
+    if self._fused():
+      return (lambda: self._grad_step_head(c, k, pipe, 'a'),
+              lambda: self._grad_step_head(c, k, pipe, 'b'), tail, opt)
+    return None, lambda: self._grad_step_head(c, k, pipe), tail, opt
 
-  def _grad_step_head(self, c, k, pipe=None, part=None):
+  def _split_step(self, parts, k):
+    self._dp.split_step(*parts, k=k, defer=self._defer_fc, branch_first=self.branch_first,
+                        pieces=self._FC_PIECES)
+
+  def _grad_step_head(self, c, k, pipe, part=None):
     """part None: the whole head; 'a': up to the conv forward; 'b': the rest."""
-    pipe = self.pipeline if pipe is None else pipe
     if part != 'b':
       if not pipe:
         self._prefetch(c)
@@ -759,96 +747,45 @@ class DQNAgent(object):
       self._forward_pair(c)
     y, g = self._loss(self._pbuf[c], c)
     f = self._bwd_first()
-    self._tail_riders = None
+    riders = self._tail_riders = self._tail_head = None
     if pipe and self._rides():      # priority write-back -> sample -> gather ride in launches f..2
-      self._head = None
-      with self._replay.memory.recording() as riders:
-        self._post_loss(self._pbuf[c])
-        self._prefetch(1 - c)
-      riders = self._place_riders(riders)
+      riders, self._tail_head = self._record_riders(c)
       n = self._SPLIT - f
-      self._hip['online'].backward(g, groups=(f, self._SPLIT), riders=riders[:n])
-      self._tail_riders = riders[n:] or None     # the fused path's gather rides in launch 3
-      self._tail_head, self._head = self._head, None
-    else:
-      self._hip['online'].backward(g, groups=(f, self._SPLIT))
+      # (the fused path's gather rides in launch 3: the tail's)
+      riders, self._tail_riders = riders[:n], riders[n:] or None
+    self._hip_backward(g, k, (f, self._SPLIT), riders)
     self._dout = g
 
-  def _grad_step_tail(self, c, k, pipe=None):
-    pipe = self.pipeline if pipe is None else pipe
+  def _grad_step_tail(self, c, k, pipe):
     g = self._dout
     if self._rides():               # the target head on the gathered batch rides in launches 3-6
       if not pipe:
         self._post_loss(self._pbuf[c])
-      f = self._bwd_first()
-      self._hip['online'].backward(g, groups=(self._SPLIT, 7),
-                                   head=self._tail_head if pipe else None,
-                                   riders=self._tail_riders if pipe else None, head_from=self._bwd_head_from())
-      self._tail_head = self._tail_riders = None
-    elif pipe:
-      main = torch.cuda.current_stream(self._device)
-      ev = torch.cuda.Event()
-      ev.record(main)
-      self._side.wait_event(ev)
-      with torch.cuda.stream(self._side):
-        self._post_loss(self._pbuf[c])
-        self._prefetch(1 - c)
-      self._hip['online'].backward(g, groups=(self._SPLIT, 7))
-      main.wait_stream(self._side)
+      self._hip_backward(g, k, (self._SPLIT, 7), self._tail_riders, self._tail_head)
     else:
-      self._post_loss(self._pbuf[c])
-      self._hip['online'].backward(g, groups=(self._SPLIT, 7))
+      self._beside_prefetch(c, pipe, lambda: self._hip_backward(g, k, (self._SPLIT, 7)))
 
   def _grad_buckets(self):
-    fp = self.online_convnet.fp
-    o = fp.offsets['fc1_w'][0]
-    return fp.grad[o:], fp.grad[:o]           # fc1 + fc2 (final after the head), convs
+    return data_parallel.grad_buckets(self.online_convnet.fp)
 
   # fc-bucket all-reduce pieces (N > 1).  4 pieces pipeline each piece's Adam part
   # behind its all-reduce, but with a one-rank RCCL group (bench --force-dist) they
   # cost 174 -> 212 us per step in launches; 1 until an 8-GPU measurement says otherwise.
   _FC_PIECES = 1
 
-  def _fc_pieces(self, lo, hi):
-    """[lo, hi) in _FC_PIECES ranges, every boundary a multiple of 4 floats."""
-    n = self._FC_PIECES
-    step = -(-(hi - lo) // (4 * n)) * 4
-    return [(a, min(a + step, hi)) for a in range(lo, hi, step)]
-
-  def _join_fc(self):
-    """The main stream waits for a deferred fc all-reduce + update (_split_step)."""
-    if self._fc_pending is not None:
-      torch.cuda.current_stream(self._device).wait_event(self._fc_pending)
-      self._fc_pending = None
-
-  def _conv_group(self):
-    """A second communicator over the same ranks: its all-reduce is not queued behind
-    the fc bucket's on the first one's internal stream.  Created on first use, which
-    every rank reaches at the same step."""
-    if self._pg_conv is None:
-      import torch.distributed as dist
-      self._pg_conv = dist.new_group(ranks=dist.get_process_group_ranks(self._pg),
-                                     backend=dist.get_backend(self._pg))
-    return self._pg_conv
-
   def _sharded(self):
-    """shard_optimizer in effect: N > 1 (or forced collectives) with TF1 Adam."""
-    if self._peer is not None:      # each learner keeps its own slice's moments
+    """The optimizer's moments are sharded: the peer exchange (each learner keeps its own
+    slice's), or shard_optimizer in effect (Exchange.sharded)."""
+    if self._peer is not None:
       return True
-    return (self.shard_optimizer and self._pg is not None and isinstance(self._opt, ops.TF1Adam)
-            and (self._world() > 1 or parallel.FORCE_COLLECTIVES))
-
-  def _world(self):
-    import torch.distributed as dist
-    return dist.get_world_size(self._pg)
+    return self._dp is not None and self._dp.sharded()
 
   def _shard_bounds(self):
-    """(lo, n): the sharded range [lo, n) of the flat buffer -- the fc bucket minus a head
-    of fewer than 4N floats, so that it splits into N equal 16-byte-aligned slices; the
-    head joins the conv bucket (all-reduced, replicated update)."""
-    n = self.online_convnet.fp.grad.numel()
-    o = n - self._grad_buckets()[0].numel()
-    return o + (n - o) % (4 * self._world()), n
+    return self._dp.shard_bounds()
+
+  def _gather_opt_state(self):
+    if self._sharded():
+      self._dp.gather_opt_state()
 
   # with the optimizer fused into the backward (single replica), also write the gradients
   # it consumes to the flat gradient buffer (``_store_grads``); bench.py turns it off.
@@ -876,116 +813,6 @@ class DQNAgent(object):
   # N > 1: capture the fc bucket's branch before the backward tail instead of after it
   branch_first = False
 
-  def _gather_opt_state(self):
-    """ZeRO-1: every rank's Adam moments of the sharded range, slice r from rank r (a
-    collective: every rank calls it, e.g. from bundle_and_checkpoint)."""
-    if not self._sharded():
-      return
-    lo, n = self._shard_bounds()
-    torch.cuda.synchronize(self._device)
-    for t in (self._opt.m, self._opt.v):
-      parallel.all_gather_(t[lo:n], self._pg)
-    torch.cuda.synchronize(self._device)
-
-  def _split_step(self, head_a, head_b, tail, opt, k=0):
-    """head | tail on the main stream with the fc bucket's all-reduce on the comm
-    stream beside the tail; with TF1 Adam the fc parameters' update follows their
-    all-reduce on the comm stream (hidden under the conv bucket's all-reduce) and
-    only the conv parameters' update (which advances the beta powers) is left
-    after the join: same arithmetic, split in two launches (dq_adam_tf1_part).
-    In the learner-only loop (_defer_fc, fused Rainbow head split in head_a | head_b)
-    the join moves to the next step, between its conv and fc forward launches: the
-    fc all-reduce then runs under this step's tail AND the next step's convs, and
-    the conv bucket goes over a second communicator so it does not wait behind it.
-    Every launch keeps its inputs: the next step's convs read no fc parameter, its
-    fc launches wait for the update, and Adam's beta-power slots alternate (the fc
-    part reads slot k while the conv part writes slot 1 - k)."""
-    main = torch.cuda.current_stream(self._device)
-    fc, conv = self._grad_buckets()
-    split_opt = isinstance(self._opt, ops.TF1Adam)
-    defer = self._defer_fc and split_opt and head_a is not None
-    grad = self.online_convnet.fp.grad
-    o = grad.numel() - fc.numel()
-    if head_a is not None:
-      head_a()
-    self._join_fc()
-    head_b()
-    ev = torch.cuda.Event()
-    ev.record(main)
-    # the tail is issued (captured) before the comm branch, so in a captured graph it is the
-    # first child of the head's last launch and stays on that launch's hardware queue -- the
-    # all-reduce branch takes the other one (a fork to another queue costs ~10 us on the
-    # critical path, measured with the branch captured first; branch_first re-measures it)
-    if not self.branch_first:
-      tail()
-    last, conv, o = self._fc_branch(ev, grad, conv, o, k, split_opt)
-    if self.branch_first:
-      tail()
-    if defer:
-      self._ar_conv(conv, True)
-      self._fc_pending = torch.cuda.Event()
-      self._fc_pending.record(last)
-    else:
-      self._ar_conv(conv, False)
-      main.wait_stream(last)
-    if split_opt:
-      self._opt.step_part(grad, 0, o, slot=k, bump=True)
-    else:
-      opt()
-
-  def _fc_branch(self, ev, grad, conv, o, k, split_opt):
-    """The fc bucket's exchange and update on the comm stream (forked at event ev, after
-    the backward launch that leaves fc1 / fc2's gradients final).  Returns (the stream to
-    join, the conv bucket, its end offset)."""
-    self._comm.wait_event(ev)
-    # The fc bucket as _FC_PIECES all-reduces back to back on the comm stream; each
-    # piece's Adam part runs on a second stream behind its own all-reduce, under the
-    # next piece's (an HBM-bound update beside a link-bound collective).  Elementwise
-    # ops: bitwise the one-bucket result.  (Blocking collectives + events rather than
-    # async work handles, which graph capture does not survive.)
-    last = self._comm
-    if self._sharded():
-      # ZeRO-1: reduce-scatter the fc bucket, TF1 Adam on this rank's slice only (1/N of
-      # the fc update's 112 MB), all-gather the updated parameters -- the same bytes over
-      # the links as the all-reduce; the other slices' moments live on their owners
-      lo, n = self._shard_bounds()
-      S = (n - lo) // self._world()
-      r = torch.distributed.get_rank(self._pg)
-      # all three on the comm stream: they are dependent, so a second stream for the
-      # update buys no overlap -- and that arrangement (comm -> second stream -> comm) made
-      # the captured chunk graphs segfault in hipStreamEndCapture on ROCm 7.2 (DESIGN §6;
-      # the repro is tools/capture_fork_repro.py, outside the product)
-      with torch.cuda.stream(self._comm):
-        if self._rccl is not None:
-          self._rccl[0].reduce_scatter_mean_(grad[lo:n])
-        else:
-          parallel.reduce_scatter_mean_(grad[lo:n], self._pg)
-        self._opt.step_part(grad, lo + r * S, lo + (r + 1) * S, slot=k, bump=False)
-        if self._rccl is not None:
-          self._rccl[0].all_gather_(self._opt.params[lo:n])
-        else:
-          parallel.all_gather_(self._opt.params[lo:n], self._pg)
-      conv, o = grad[:lo], lo                 # the head of the fc bucket joins the conv bucket
-    else:
-      pieces = self._fc_pieces(o, grad.numel()) if split_opt else [(o, grad.numel())]
-      # one piece: its update right behind it on the comm stream (measured equal to the
-      # second stream at one rank, 6,040 / 6,007 vs 6,027 / 6,014 steps/s, and one queue
-      # hop fewer in the captured graphs)
-      one = len(pieces) == 1
-      for lo, hi in pieces:
-        with torch.cuda.stream(self._comm):
-          self._ar_fc(grad[lo:hi])
-          if split_opt and one:
-            self._opt.step_part(grad, lo, hi, slot=k, bump=False)
-        if split_opt and not one:
-          e = torch.cuda.Event()
-          e.record(self._comm)
-          self._comm_opt.wait_event(e)
-          with torch.cuda.stream(self._comm_opt):
-            self._opt.step_part(grad, lo, hi, slot=k, bump=False)
-          last = self._comm_opt
-    return last, conv, o
-
   def _post_loss(self, t):
     """Work that needs the loss but not the gradient (PER priority write-back)."""
 
@@ -997,11 +824,6 @@ class DQNAgent(object):
       self._opt.step(self.online_convnet.fp.grad, slot=k)
     else:
       self._opt.step_multi([prm.grad for prm in self.online_convnet.parameters()], slot=k)
-
-  def _allreduce_grads(self):
-    if not self._collective():
-      return
-    parallel.allreduce_mean_(self.online_convnet.fp.grad, self._pg)
 
   def _discard_prefetch(self):
     if self._has_prefetch:
@@ -1084,14 +906,19 @@ class DQNAgent(object):
     mem.reserve_rng(self._batch_size, steps=K)
     self._graph_sets[key].replay()
     self._opt_steps += K
-    last = self._cbv[p][K - 2]          # the batch the chunk's last step trained on
-    self._replay._out = last
-    self._replay.unpack_transition(last)
-    self._slot = (k0 + K) % 2
     self._cb_ready = p
-    self._has_prefetch = True
-    self._prefetch_add_count = int(mem.add_count)
-    self._last_train_add_count = int(mem.add_count)
+    # (the batch the chunk's last step trained on)
+    self._step_done(self._cbv[p][K - 2], (k0 + K) % 2, True)
+
+  def _step_done(self, batch, slot, has_prefetch):
+    """The host's books after a gradient step (or a chunk's last one) on ``batch``: the
+    replay's last transition, the slot the next step reads, and whether its batch is
+    prefetched there -- valid while nothing is added or drawn (_interleaved)."""
+    self._replay._out = batch
+    self._replay.unpack_transition(batch)
+    self._slot = slot
+    self._has_prefetch = has_prefetch
+    self._prefetch_add_count = self._last_train_add_count = int(self._replay.memory.add_count)
     self._selects_since_train = 0
 
   # The prefetch of step t+1 (drawn right after step t's priority write-back) is
@@ -1123,37 +950,24 @@ class DQNAgent(object):
     graphs = self._graph_sets.get(pipe)
     if self._split_allreduce():
       if graphs is not None:
-        self._split_step(*[None if g is None else g.replay for g in graphs[0][k]], k=k)
-      elif self._head_splits():
-        self._split_step(lambda: self._grad_step_head(c, k, pipe, 'a'),
-                         lambda: self._grad_step_head(c, k, pipe, 'b'),
-                         lambda: self._grad_step_tail(c, k, pipe),
-                         lambda: self._device_opt_step(k), k=k)
-        self._eager_steps[pipe] += 1
+        self._split_step([None if g is None else g.replay for g in graphs[0][k]], k)
       else:
-        self._split_step(None, lambda: self._grad_step_head(c, k, pipe),
-                         lambda: self._grad_step_tail(c, k, pipe),
-                         lambda: self._device_opt_step(k), k=k)
+        self._split_step(self._split_parts(c, k, pipe), k)
         self._eager_steps[pipe] += 1
     elif graphs is not None:
       graphs[0][k].replay()
       if self._collective():
-        self._allreduce_grads()
+        self._dp.allreduce_grads()
         graphs[1][k].replay()
     else:
       self._grad_step(c, k, pipe)
-      self._allreduce_grads()
+      if self._collective():
+        self._dp.allreduce_grads()
       self._device_opt_step(k)
       self._trace_step(self._UNROLL + k, c)
       self._eager_steps[pipe] += 1
     self._opt_steps += 1
-    self._replay._out = self._pbuf[c]
-    self._replay.unpack_transition(self._pbuf[c])
-    self._slot = 1 - c
-    self._has_prefetch = pipe
-    self._prefetch_add_count = int(mem.add_count)
-    self._last_train_add_count = int(mem.add_count)
-    self._selects_since_train = 0
+    self._step_done(self._pbuf[c], 1 - c, pipe)
     if graphs is None and self.use_hip_graph and self._eager_steps[pipe] >= 3:
       self._capture(pipe)
 
@@ -1162,24 +976,16 @@ class DQNAgent(object):
     g = self._graph_sets.get(self.pipeline)
     return None if g is None else g[0]
 
-  def _capture(self, pipe=None):
+  def _capture(self, pipe):
     """Two graphs, one per gradient-step parity k (pipeline slot and Adam
     beta-power slot both alternate with k); with one GPU the optimizer is in the
     same graph, with N GPUs it is a second graph after the RCCL all-reduce."""
-    pipe = self.pipeline if pipe is None else pipe
     torch.cuda.synchronize(self._device)
     graphs, graphs_opt, pool = [], [], self._graph_pool
     if self._split_allreduce():
       for k in (0, 1):
-        c = k
-        if self._head_splits():
-          fns = (lambda: self._grad_step_head(c, k, pipe, 'a'),
-                 lambda: self._grad_step_head(c, k, pipe, 'b'))
-        else:
-          fns = (None, lambda: self._grad_step_head(c, k, pipe))
-        fns += (lambda: self._grad_step_tail(c, k, pipe), lambda: self._device_opt_step(k))
         parts = []
-        for fn in fns:
+        for fn in self._split_parts(k, k, pipe):
           gr = None
           if fn is not None:
             gr = torch.cuda.CUDAGraph()
@@ -1268,6 +1074,20 @@ class DQNAgent(object):
   def _online_q(self, x):
     return self._q_from_output(self.online_convnet(x))
 
+  def _act_graph(self, exe, x):
+    """(graph, its Q-values tensor): a batch-1 executor's forward on x and the Q reduction,
+    warmed up on a stream of its own and captured."""
+    main = torch.cuda.current_stream(self._device)
+    warm = torch.cuda.Stream(self._device)
+    warm.wait_stream(main)
+    with torch.cuda.stream(warm):
+      self._q_from_output(exe.forward(x))
+    main.wait_stream(warm)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+      q = self._q_from_output(exe.forward(x))
+    return g, q
+
   def _act_q(self, state_np):
     """Q-values for action selection on the HIP CNN at batch 1: the forward and
     the Q reduction are one captured graph; the state goes up through a pinned
@@ -1277,16 +1097,7 @@ class DQNAgent(object):
       exe = HipNatureCNN(self.online_convnet, 1)
       x = torch.zeros((1, 84, 84, self.stack_size), dtype=torch.float32, device=self._device)
       pin = torch.empty(x.shape, dtype=torch.float32).pin_memory()
-      main = torch.cuda.current_stream(self._device)
-      warm = torch.cuda.Stream(self._device)
-      warm.wait_stream(main)
-      with torch.cuda.stream(warm):
-        self._q_from_output(exe.forward(x))
-      main.wait_stream(warm)
-      g = torch.cuda.CUDAGraph()
-      with torch.cuda.graph(g):
-        q = self._q_from_output(exe.forward(x))
-      self._act = (exe, x, pin, g, q)
+      self._act = (exe, x, pin) + self._act_graph(exe, x)
     exe, x, pin, g, q = self._act
     scale = 1.0 / 255.0 if np.dtype(self.observation_dtype) == np.uint8 else 1.0
     np.multiply(state_np, scale, out=pin.numpy(), casting='unsafe')
@@ -1305,20 +1116,7 @@ class DQNAgent(object):
       dt = torch.float32 if np.dtype(self.observation_dtype) == np.float32 else torch.float64
       x = torch.zeros(exe.D, dtype=dt, device=self._device)
       pin = torch.empty(exe.D, dtype=dt).pin_memory()
-      g = None
-      if self.use_hip_graph:
-        main = torch.cuda.current_stream(self._device)
-        warm = torch.cuda.Stream(self._device)
-        warm.wait_stream(main)
-        with torch.cuda.stream(warm):
-          self._q_from_output(exe.forward(x))
-        main.wait_stream(warm)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-          q = self._q_from_output(exe.forward(x))
-        self._act = (exe, x, pin, g, q)
-      else:
-        self._act = (exe, x, pin, None, None)
+      self._act = (exe, x, pin) + (self._act_graph(exe, x) if self.use_hip_graph else (None, None))
     exe, x, pin, g, q = self._act
     pin.numpy()[:] = np.asarray(state_np).reshape(-1)
     x.copy_(pin, non_blocking=True)
@@ -1392,7 +1190,10 @@ class DQNAgent(object):
       self._defer_fc = False
       self._join_fc()
       self._peer_flush()
-    self._maybe_check_replicas()
+    if self._dp is not None:
+      self._dp.maybe_check_replicas(self._opt_steps, self.replica_check_period,
+                                    lambda: self.check_exchange(collective=True),
+                                    self.replica_report)
 
   def _train_gradient_steps(self, n):
     while n > 0:
@@ -1431,23 +1232,13 @@ class DQNAgent(object):
                  for p in (False, True))
     return all(('chunk', self._UNROLL, k) in self._graph_sets for k in (0, 1))
 
-  def _captures_collectives(self):
-    """N > 1 over the learner's own RCCL communicators with the split fused-head schedule:
-    the gradient all-reduces are captured inside the learner loop's chunk graphs (gloo's
-    host-side collectives cannot be, torch.distributed's are not)."""
-    if not self._collective():
-      return False
-    import torch.distributed as dist
-    # (torch.distributed's own collectives are never captured: parallel.collectives_capturable)
-    return (dist.get_backend(self._pg) == 'nccl' and self._rccl is not None and
-            self._split_allreduce() and self._head_splits() and
-            isinstance(self._opt, ops.TF1Adam) and
-            parallel.collectives_capturable(self._pg, self._device, self._comm,
-                                            sharded=self._sharded(), comms=self._rccl))
-
   def _chunks_apply(self):
-    return (self._hip is not None and self.pipeline and
-            (not self._collective() or self._captures_collectives()))
+    """Chunk graphs: a single replica's or the peer exchange's pipelined HIP-CNN steps, or the
+    split fused-head schedule with its collectives captured (Exchange.captures_collectives)."""
+    if self._hip is None or not self.pipeline:
+      return False
+    return not self._collective() or self._dp.captures_collectives(
+        self._split_allreduce() and self._fused())
 
   def _chunk_ok(self):
     K, U = self._UNROLL, self.update_period
@@ -1476,8 +1267,8 @@ class DQNAgent(object):
     pending = defer and self._peer_pending
     key = ('chunk', K, k0) + ((pending,) if defer else ())
     g = self._graph_sets.get(key)
+    self._join_fc()                   # (a capture: nothing outside it may be pending)
     if g is None:
-      self._join_fc()                 # nothing outside the capture may be pending
       torch.cuda.synchronize(self._device)
       g = torch.cuda.CUDAGraph()
       if not self._collective():
@@ -1500,27 +1291,16 @@ class DQNAgent(object):
         with torch.cuda.graph(g, pool=self._graph_pool, capture_error_mode='thread_local'):
           for j in range(K):
             k = (k0 + j) % 2
-            self._split_step(lambda k=k: self._grad_step_head(k, k, True, 'a'),
-                             lambda k=k: self._grad_step_head(k, k, True, 'b'),
-                             lambda k=k: self._grad_step_tail(k, k, True),
-                             lambda k=k: self._device_opt_step(k), k=k)
+            self._split_step(self._split_parts(k, k, True), k)
           self._join_fc()
       self._graph_pool = g.pool()
       self._graph_sets[key] = g
-    else:
-      self._join_fc()
     mem.reserve_rng(self._batch_size, steps=K)
     g.replay()
     self._peer_pending = defer        # the last step's gather is left to the next chunk / flush
     self._opt_steps += K
     c = (k0 + K - 1) % 2
-    self._replay._out = self._pbuf[c]
-    self._replay.unpack_transition(self._pbuf[c])
-    self._slot = 1 - c
-    self._has_prefetch = True
-    self._prefetch_add_count = int(mem.add_count)
-    self._last_train_add_count = int(mem.add_count)
-    self._selects_since_train = 0
+    self._step_done(self._pbuf[c], 1 - c, True)
 
   def _train_step(self):
     """dqn_agent.py:418-442."""
@@ -1549,41 +1329,17 @@ class DQNAgent(object):
       self._peer.check(collective=collective)
 
   def replica_report(self):
-    """Collective (every rank of the group calls it at the same point): every replicated
-    tensor -- online and target parameters, the optimizer's moments (the sharded ranges'
-    slices gathered first, _gather_opt_state) and its state -- compared bit for bit with
-    group rank 0's (parallel.replica_report).  SURVEY 8e: identical updates keep the replicas
-    bit-identical; this is the check that they did."""
+    """Collective: every replicated tensor -- online and target parameters, the optimizer's
+    moments and state -- compared bit for bit with group rank 0's (Exchange.replica_report)."""
     assert self._pg is not None, 'replica_report needs a process group'
-    self._join_fc()
-    torch.cuda.synchronize(self._device)
-    self._gather_opt_state()
     named = {'online': self.online_convnet.fp.flat, 'target': self.target_convnet.fp.flat}
-    for k, v in sorted(vars(self._opt).items()):
-      if isinstance(v, torch.Tensor) and v.data_ptr() != self.online_convnet.fp.flat.data_ptr():
-        named['opt_' + k.lstrip('_')] = v
-    return parallel.replica_report(named, self._pg)
+    named.update(('opt_' + k.lstrip('_'), v) for k, v in self._opt_tensors())
+    return self._dp.replica_report(named, gather=self._sharded())
 
   # data-parallel learner loop: every replica_check_period gradient steps (crossed inside a
   # train_gradient_steps call, which every rank makes with the same n), the replicas are
   # compared bit for bit and a divergence raises on every rank (0: never)
   replica_check_period = 100_000
-  _next_replica_check = None
-
-  def _maybe_check_replicas(self):
-    if self._pg is None or not self.replica_check_period:
-      return
-    if self._next_replica_check is None:
-      self._next_replica_check = self._opt_steps + self.replica_check_period
-    if self._opt_steps < self._next_replica_check:
-      return
-    self._next_replica_check = self._opt_steps + self.replica_check_period
-    self.check_exchange(collective=True)
-    rep = self.replica_report()
-    bad = {k: v['differing'] for k, v in rep.items() if not v['in_sync']}
-    if bad:
-      raise RuntimeError('data-parallel replicas diverged after %d gradient steps: elements '
-                         'differing from rank 0, per rank: %r' % (self._opt_steps, bad))
 
   def mean_loss(self):
     """Mean loss of the last gradient step (the summary scalar, dqn:318-321); the fused
@@ -1608,9 +1364,7 @@ class DQNAgent(object):
   # ---------------------------------------------------------- checkpoints
   def _ckpt_tensors(self):
     d = {'online': self.online_convnet.fp.flat, 'target': self.target_convnet.fp.flat}
-    for k, v in vars(self._opt).items():
-      if isinstance(v, torch.Tensor) and v.data_ptr() != self.online_convnet.fp.flat.data_ptr():
-        d['opt_' + k] = v
+    d.update(('opt_' + k, v) for k, v in self._opt_tensors())    # the file's keys: a format
     return d
 
   def _rank_dir(self, checkpoint_dir):
@@ -1621,8 +1375,7 @@ class DQNAgent(object):
     would otherwise collide in a shared run directory."""
     if self._pg is None:
       return checkpoint_dir
-    import torch.distributed as dist
-    return os.path.join(checkpoint_dir, 'rank%d' % dist.get_rank(self._pg))
+    return data_parallel.rank_dir(self._pg, checkpoint_dir)
 
   def bundle_and_checkpoint(self, checkpoint_dir, iteration_number):
     """dqn_agent.py:482-510 (torch tensors instead of a tf.train.Saver).  With a process

@@ -24,7 +24,7 @@ class FlatParams(object):
   multiple): zero padding at the end so that the range from parameter ``name`` to the end
   is a whole number of ``multiple`` floats (the Nature-CNN nets: the fc bucket splits into
   world equal 16-byte slices for every world size 1..8 -- the data-parallel exchanges'
-  shards, DQNAgent._shard_bounds; the padding keeps zero gradients, so every optimizer
+  shards, data_parallel.shard_bounds; the padding keeps zero gradients, so every optimizer
   leaves it zero)."""
 
   def __init__(self, shapes, device, tail_align=None):

@@ -1,8 +1,9 @@
 """Dump the N > 1 learner loop's captured chunk graph (one-rank RCCL, every collective
 executed) as Graphviz dot and print its node/edge structure: which node each kernel waits
 on, and every edge that crosses from the comm stream's branch into the main chain.
+--single: the single replica's chunk graph instead (no process group).
 
-    python tools/dist_graph_dot.py OUTDIR [--zero 0|1]
+    python tools/dist_graph_dot.py OUTDIR [--zero 0|1] [--single]
 
 A diagnostic for DESIGN.md §6 (what the next step's conv1 waits on); not a product path.
 """
@@ -52,18 +53,22 @@ def short(label):
 def main():
   out = sys.argv[1] if len(sys.argv) > 1 else 'gpurun_out/dist_dot'
   zero = int(sys.argv[sys.argv.index('--zero') + 1]) if '--zero' in sys.argv else 0
+  single = '--single' in sys.argv
   os.makedirs(out, exist_ok=True)
   torch.cuda.CUDAGraph = _DbgGraph
   from dopamine_amd import parallel
   import bench
-  parallel.FORCE_COLLECTIVES = True
-  os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
-  os.environ.setdefault('MASTER_PORT', '29541')
   dev = torch.device('cuda', 0)
   torch.cuda.set_device(0)
-  dist.init_process_group('nccl', rank=0, world_size=1, device_id=dev)
-  agent = bench.build_agent(9, 1_000_000, 32, dev, pg=dist.group.WORLD,
-                            **({'shard_optimizer': True} if zero else {}))
+  if single:
+    agent = bench.build_agent(9, 1_000_000, 32, dev)
+  else:
+    parallel.FORCE_COLLECTIVES = True
+    os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
+    os.environ.setdefault('MASTER_PORT', '29541')
+    dist.init_process_group('nccl', rank=0, world_size=1, device_id=dev)
+    agent = bench.build_agent(9, 1_000_000, 32, dev, pg=dist.group.WORLD,
+                              **({'shard_optimizer': True} if zero else {}))
   import random
   random.seed(0)
   bench.fill_synthetic(agent._replay.memory, 9, seed=1)
@@ -106,7 +111,8 @@ def main():
                                                for p in preds[n])))
   print(open(os.path.join(out, 'chunk_graph_nodes.txt')).read())
   agent.close()
-  dist.destroy_process_group()
+  if not single:
+    dist.destroy_process_group()
 
 
 if __name__ == '__main__':

@@ -9,9 +9,9 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402
 from dopamine_amd import parallel  # noqa: E402
-from dopamine_amd.agents.dqn import dqn_agent  # noqa: E402
+from dopamine_amd.agents.dqn import data_parallel  # noqa: E402
 
-dqn_agent.DQNAgent._ar_conv = lambda self, t, second: parallel.allreduce_mean_(
-    t, self._conv_group() if second else self._pg)
+data_parallel.Exchange._ar_conv = lambda self, t, second: parallel.allreduce_mean_(
+    t, self._conv_group() if second else self.pg)
 sys.argv = [sys.argv[0], '--force-dist', '--zero', '0', '--skip-cpu-baseline', '--skip-configs'] + sys.argv[1:]
 bench.main()

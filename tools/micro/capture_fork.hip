@@ -1,6 +1,7 @@
 // HIP-graph capture of origin -> A -> B -> A -> origin (stream A forks stream B and joins it
 // back before A joins the origin), plain HIP: the pattern of the ZeRO-1 update on a second
-// stream (dqn_agent._fc_branch, zero_update_stream) without torch, RCCL or this package.
+// stream (data_parallel.Exchange._fc_branch, zero_update_stream) without torch, RCCL or this
+// package.
 //   hipcc --offload-arch=gfx950 -O2 tools/micro/capture_fork.hip -o tools/micro/capture_fork.bin
 //   ./tools/micro/capture_fork.bin <steps>
 #include <hip/hip_runtime.h>

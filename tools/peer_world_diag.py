@@ -56,7 +56,7 @@ def main():
   print('%-8s %12s %12s  ranks differing from rank 0' % ('tensor', 'max |r - r0|', 'max |r0-ref|'))
   n_all = res[0].size
   o = offs['fc1_w'][0]
-  lo = o + (n_all - o) % (4 * world)           # DQNAgent._shard_bounds
+  lo = o + (n_all - o) % (4 * world)           # data_parallel.shard_bounds
   S = (n_all - lo) // world
   for r in range(1, world):
     bad = np.flatnonzero(res[r] != res[0])
