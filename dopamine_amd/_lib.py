@@ -9,7 +9,7 @@ import os
 from dopamine_amd import _build
 from dopamine_amd._build import HEADER, LIB_PATH  # noqa: F401
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 OK = 0
 (ST_OK, ST_EMPTY_TREE, ST_MAX_ATTEMPTS, ST_TAPE_EXHAUSTED, ST_NEG_PRIORITY, ST_TOO_FEW, ST_BAD_INDEX,
  ST_BROADCAST) = range(8)
@@ -86,6 +86,21 @@ class MlpParams(ctypes.Structure):
 
 class MlpActs(ctypes.Structure):
   _fields_ = [('x0', ctypes.c_void_p), ('h', ctypes.c_void_p * 4), ('out', ctypes.c_void_p)]
+
+
+FOURIER_MAX_IN, FOURIER_MAX_OUT, FOURIER_MAX_FEATURES = 16, 64, 16383    # DQ_FOURIER_MAX_*
+
+
+class FourierParams(ctypes.Structure):
+  """dq_fourier_params: the Fourier-basis network's head over a flat parameter (or gradient)
+  buffer."""
+  _fields_ = [('in_dim', ctypes.c_int32), ('order', ctypes.c_int32), ('n_out', ctypes.c_int32),
+              ('pad_', ctypes.c_int32), ('w', ctypes.c_void_p),
+              ('in_min', ctypes.c_float * 16), ('in_range', ctypes.c_float * 16)]
+
+
+class FourierActs(ctypes.Structure):
+  _fields_ = [('s', ctypes.c_void_p), ('phi', ctypes.c_void_p), ('out', ctypes.c_void_p)]
 
 
 class C51Target(ctypes.Structure):
@@ -188,6 +203,7 @@ SIGNATURES = {
     'dq_adam_tf1_part': [_P, _P, _P, _P, _P, _I32, _I64, _F, _F, _F, _F, _I32, _P],
     'dq_adam_tf1_multi': [ctypes.POINTER(TensorList), _P, _I32, _F, _F, _F, _F, _P],
     'dq_rmsprop_tf1': [_P, _P, _P, _P, _P, _I64, _F, _F, _F, _F, _I32, _P],
+    'dq_sgd_tf1': [_P, _P, _I64, _F, _P],
     'dq_sync_copy': [_P, _P, _I64, _P],
     'dq_cnn_forward': [ctypes.POINTER(CnnParams), _I32, _P, ctypes.POINTER(CnnActs), _P, _P],
     'dq_cnn_forward_pair': [ctypes.POINTER(CnnParams), _P, ctypes.POINTER(CnnActs), _P,
@@ -235,6 +251,11 @@ SIGNATURES = {
     'dq_mlp_backward_layer': [ctypes.POINTER(MlpParams), ctypes.POINTER(MlpParams), _I32,
                               ctypes.POINTER(MlpActs), _P, ctypes.POINTER(MlpActs), _P, _I32, _I32,
                               _P],
+    'dq_fourier_features': [_I32, _I32],
+    'dq_fourier_forward': [ctypes.POINTER(FourierParams), _I32, _P, _I32,
+                           ctypes.POINTER(FourierActs), _P],
+    'dq_fourier_backward': [ctypes.POINTER(FourierParams), ctypes.POINTER(FourierParams), _I32,
+                            ctypes.POINTER(FourierActs), _P, _P],
     'dq_iqn_head_forward': [ctypes.POINTER(IqnHead), _I32, _I32, _P, _P, ctypes.POINTER(IqnActs),
                             _P, _P],
     'dq_iqn_head_backward': [ctypes.POINTER(IqnHead), ctypes.POINTER(IqnHead), _I32, _I32, _P,

@@ -146,9 +146,10 @@ class DQNAgent(object):
     self.use_hip_graph = use_hip_graph
     self.pipeline = pipeline
     self.use_hip_cnn = use_hip_cnn
-    # the classic-control MLPs on the HIP executor (dopamine_amd/mlp.py): None -- on for the
-    # gym networks but CartpoleDQNNetwork (config 1 keeps its PyTorch path); True / False
-    # -- on for every gym network / PyTorch everywhere.  Single replica only.
+    # the classic-control MLPs on the HIP executor (dopamine_amd/mlp.py) and the Fourier-basis
+    # networks on theirs (dopamine_amd/fourier.py): None -- on for the gym networks but
+    # CartpoleDQNNetwork (config 1 keeps its PyTorch path); True / False -- on for every gym
+    # network / PyTorch everywhere.  Single replica only.
     self.use_hip_mlp = use_hip_mlp
     self.fuse_optimizer = fuse_optimizer
     self.pair_forward = pair_forward
@@ -326,7 +327,17 @@ class DQNAgent(object):
 
   def _is_gym_network(self):
     return (isinstance(self.network, type) and
-            issubclass(self.network, networks.BasicDiscreteDomainNetwork))
+            issubclass(self.network, (networks.BasicDiscreteDomainNetwork,
+                                      networks.FourierDQNNetwork)))
+
+  def _mlp_executor(self, net, batch_size, keep):
+    """The HIP executor of a classic-control network at this batch size: HipFourier for the
+    Fourier-basis networks (keep: its forward stores what the backward reads), else HipMLP."""
+    if isinstance(net, networks.FourierDQNNetwork):
+      from dopamine_amd.fourier import HipFourier
+      return HipFourier(net, batch_size, keep=keep)
+    from dopamine_amd.mlp import HipMLP
+    return HipMLP(net, batch_size)
 
   def _build_mlp(self):
     """The HIP MLP executors (one online, one per pipeline slot for the target), or None."""
@@ -338,10 +349,9 @@ class DQNAgent(object):
     if not self._is_gym_network():
       raise ValueError('use_hip_mlp=True needs a classic-control network (gym_lib), got %r'
                        % (self.network,))
-    from dopamine_amd.mlp import HipMLP
     B = self._batch_size
-    return dict(online=HipMLP(self.online_convnet, B),
-                target=[HipMLP(self.target_convnet, B) for _ in range(2)])
+    return dict(online=self._mlp_executor(self.online_convnet, B, True),
+                target=[self._mlp_executor(self.target_convnet, B, False) for _ in range(2)])
 
   def _build_networks(self):
     self.online_convnet = self._make_network(self._seed)
@@ -1107,12 +1117,11 @@ class DQNAgent(object):
 
   def _act_q_mlp(self, state_np):
     """Q-values for action selection on the HIP MLP at batch 1, the analogue of _act_q: the
-    three launches and the Q reduction are one captured graph (use_hip_graph), the state
+    forward's launches and the Q reduction are one captured graph (use_hip_graph), the state
     goes up through a pinned staging buffer in the observation's own dtype and is cast to
     float32 in the first kernel.  (stack_size 1: the flattened state is the observation.)"""
     if self._act is None:
-      from dopamine_amd.mlp import HipMLP
-      exe = HipMLP(self.online_convnet, 1)
+      exe = self._mlp_executor(self.online_convnet, 1, False)
       dt = torch.float32 if np.dtype(self.observation_dtype) == np.float32 else torch.float64
       x = torch.zeros(exe.D, dtype=dt, device=self._device)
       pin = torch.empty(exe.D, dtype=dt).pin_memory()

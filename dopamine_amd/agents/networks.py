@@ -1,4 +1,4 @@
-"""Q-networks of the reference (atari_lib.py:85-199, gym_lib.py:75-132) in
+"""Q-networks of the reference (atari_lib.py:85-199, gym_lib.py:75-317) in
 PyTorch-ROCm, with every parameter a view into ONE flat fp32 buffer.
 
 The flat layout is the MI355X-side design choice: the TF1 Adam / RMSProp
@@ -16,6 +16,8 @@ import math
 import numpy as np
 import torch
 import torch.nn.functional as F
+
+from dopamine_amd import gin_lite
 
 
 class FlatParams(object):
@@ -215,10 +217,14 @@ class BasicDiscreteDomainNetwork(_Net):
   kernels."""
 
   MIN = MAX = None      # the domain's observation bounds (float64), set by subclasses
+  GIN_NAME = None       # the reference's configurable, whose network_size binding is honoured
 
   def __init__(self, num_actions, num_atoms=None, stack_size=1, device='cuda', seed=0,
-               network_size=(512, 512)):
-    self.A, self.N, self.sizes = num_actions, num_atoms, tuple(network_size)
+               network_size=None):
+    if network_size is None:    # the gin binding (acrobot_dqn_network.network_size), or 512-512
+      bound = gin_lite.query(self.GIN_NAME) if self.GIN_NAME else {}
+      network_size = bound.get('network_size', (512, 512))
+    self.A, self.N, self.sizes = num_actions, num_atoms, tuple(int(w) for w in network_size)
     self.D = int(len(self.MIN)) * int(stack_size)
     assert stack_size == 1, 'the classic-control domains stack one observation'
     super().__init__(device, seed, init='xavier')
@@ -255,8 +261,9 @@ class CartpoleDQNNetwork(BasicDiscreteDomainNetwork):
   """gym_lib.py:113-132: rescale to [-1, 1] then FC 512-512-A."""
 
   MIN, MAX = _CARTPOLE_MIN, _CARTPOLE_MAX
+  GIN_NAME = 'cartpole_dqn_network'
 
-  def __init__(self, num_actions, device='cuda', seed=0, network_size=(512, 512), num_atoms=None,
+  def __init__(self, num_actions, device='cuda', seed=0, network_size=None, num_atoms=None,
                stack_size=1):
     assert num_atoms is None
     super().__init__(num_actions, None, stack_size, device, seed, network_size)
@@ -266,9 +273,10 @@ class CartpoleRainbowNetwork(BasicDiscreteDomainNetwork):
   """gym_lib.py:227-252 -> logits (B, A, N)."""
 
   MIN, MAX = _CARTPOLE_MIN, _CARTPOLE_MAX
+  GIN_NAME = 'cartpole_rainbow_network'
 
   def __init__(self, num_actions, num_atoms=51, stack_size=1, device='cuda', seed=0,
-               network_size=(512, 512)):
+               network_size=None):
     super().__init__(num_actions, num_atoms, stack_size, device, seed, network_size)
 
 
@@ -276,8 +284,9 @@ class AcrobotDQNNetwork(BasicDiscreteDomainNetwork):
   """gym_lib.py:255-273: rescale to [-1, 1] then FC 512-512-A."""
 
   MIN, MAX = _ACROBOT_MIN, _ACROBOT_MAX
+  GIN_NAME = 'acrobot_dqn_network'
 
-  def __init__(self, num_actions, device='cuda', seed=0, network_size=(512, 512), num_atoms=None,
+  def __init__(self, num_actions, device='cuda', seed=0, network_size=None, num_atoms=None,
                stack_size=1):
     assert num_atoms is None
     super().__init__(num_actions, None, stack_size, device, seed, network_size)
@@ -287,7 +296,72 @@ class AcrobotRainbowNetwork(BasicDiscreteDomainNetwork):
   """gym_lib.py:295-317 -> logits (B, A, N)."""
 
   MIN, MAX = _ACROBOT_MIN, _ACROBOT_MAX
+  GIN_NAME = 'acrobot_rainbow_network'
 
   def __init__(self, num_actions, num_atoms=51, stack_size=1, device='cuda', seed=0,
-               network_size=(512, 512)):
+               network_size=None):
     super().__init__(num_actions, num_atoms, stack_size, device, seed, network_size)
+
+
+def fourier_multipliers(in_dim, order):
+  """gym_lib.py:153-157: itertools.product(range(order + 1), repeat=in_dim) without its first,
+  all-zero tuple, (F, D) int64: row f holds the digits of f + 1 in base order + 1, dimension
+  0 the most significant."""
+  base, F = order + 1, (order + 1) ** in_dim - 1
+  n = np.arange(1, F + 1, dtype=np.int64)[:, None]
+  return (n // base ** np.arange(in_dim - 1, -1, -1, dtype=np.int64)[None, :]) % base
+
+
+class FourierDQNNetwork(_Net):
+  """gym_lib.py:135-206 (FourierBasis, fourier_dqn_network): the observation scaled to [0, 1]
+  by the domain's MIN / MAX (no clipping), the F = (order + 1)^D - 1 features
+  cos(float32(pi) * s . m_f), and a linear layer of num_actions Q-values without a bias
+  (Xavier-uniform): the only parameter.  ``forward`` is the PyTorch path
+  (``use_hip_mlp=False``); dopamine_amd.fourier.HipFourier runs the same parameter on the HIP
+  kernels.  ``fourier_basis_order`` None: the gin binding
+  fourier_dqn_network.fourier_basis_order, or 3."""
+
+  MIN = MAX = None      # the domain's observation bounds (float64), set by subclasses
+  PI = float(np.float32(np.pi))     # np.pi enters the reference's graph as a float32 constant
+
+  def __init__(self, num_actions, device='cuda', seed=0, fourier_basis_order=None, stack_size=1):
+    if fourier_basis_order is None:
+      fourier_basis_order = gin_lite.query('fourier_dqn_network').get('fourier_basis_order', 3)
+    assert stack_size == 1, 'the classic-control domains stack one observation'
+    self.A, self.order = num_actions, int(fourier_basis_order)
+    self.D = int(len(self.MIN)) * int(stack_size)
+    if self.order < 1:
+      raise ValueError('fourier_basis_order must be >= 1, got %r' % (fourier_basis_order,))
+    self.F = (self.order + 1) ** self.D - 1
+    super().__init__(device, seed, init='xavier')
+    self._min = torch.tensor(self.MIN, dtype=torch.float32, device=device)
+    self._rng = torch.tensor(self.MAX - self.MIN, dtype=torch.float32, device=device)
+    self._mult = torch.tensor(fourier_multipliers(self.D, self.order), dtype=torch.float32,
+                              device=device)
+
+  @property
+  def n_out(self):
+    return self.A
+
+  def shapes(self):
+    return [('out_w', (self.A, self.F))]
+
+  def features(self, x):
+    """(the scaled input (B, D), the features (B, F)), float32."""
+    s = (x.reshape(x.shape[0], -1).float() - self._min) / self._rng
+    return s, torch.cos(self.PI * (s @ self._mult.t()))
+
+  def forward(self, x):
+    return F.linear(self.features(x)[1], self.fp['out_w'])
+
+
+class CartpoleFourierDQNNetwork(FourierDQNNetwork):
+  """gym_lib.py:209-224: 255 features at order 3, 510 parameters."""
+
+  MIN, MAX = _CARTPOLE_MIN, _CARTPOLE_MAX
+
+
+class AcrobotFourierDQNNetwork(FourierDQNNetwork):
+  """gym_lib.py:276-292: 4,095 features at order 3, 12,285 parameters."""
+
+  MIN, MAX = _ACROBOT_MIN, _ACROBOT_MAX

@@ -16,6 +16,19 @@ class AdamOptimizer(object):
     return 'AdamOptimizer(%r)' % self.kwargs
 
 
+class GradientDescentOptimizer(object):
+  """tf.train.GradientDescentOptimizer (dqn_acrobot.gin:23-26)."""
+
+  def __init__(self, learning_rate, **unused):
+    self.kwargs = dict(learning_rate=learning_rate)
+
+  def build(self, flat_params, segments=None):
+    return ops.TF1GradientDescent(flat_params, **self.kwargs)
+
+  def __repr__(self):
+    return 'GradientDescentOptimizer(%r)' % self.kwargs
+
+
 class RMSPropOptimizer(object):
   def __init__(self, learning_rate, decay=0.9, momentum=0.0, epsilon=1e-10, centered=False, **unused):
     self.kwargs = dict(learning_rate=learning_rate, decay=decay, momentum=momentum,

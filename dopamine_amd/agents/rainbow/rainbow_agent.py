@@ -89,6 +89,10 @@ class RainbowAgent(dqn_agent.DQNAgent):
                summary_writer=None,
                summary_writing_frequency=500,
                **kwargs):
+    if isinstance(network, type) and issubclass(network, networks.FourierDQNNetwork):
+      # gym_lib.py:172-206: fourier_dqn_network returns bare Q-values, no distribution
+      raise ValueError('%s needs a network with a distributional head; the Fourier-basis '
+                       'networks return Q-values (use DQNAgent)' % type(self).__name__)
     vmax = float(vmax)
     self._num_atoms = num_atoms
     self._vmax = vmax

@@ -846,6 +846,26 @@ __global__ __launch_bounds__(256) void k_rmsprop(float* var, const float* grad, 
   }
 }
 
+// tf.train.GradientDescentOptimizer (ApplyGradientDescent): var -= lr * g, the product
+// rounded, then the difference.  A float4 body (n4 vectors; 0 when a buffer is not 16-byte
+// aligned) and a scalar tail.
+__global__ __launch_bounds__(256) void k_sgd(float* __restrict__ var, const float* __restrict__ grad,
+                                             int64_t n, int64_t n4, float lr) {
+  const int64_t first = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = first; i < n4; i += stride) {
+    float4 p = ((float4*)var)[i];
+    const float4 g = ((const float4*)grad)[i];
+    p.x = __fsub_rn(p.x, __fmul_rn(lr, g.x));
+    p.y = __fsub_rn(p.y, __fmul_rn(lr, g.y));
+    p.z = __fsub_rn(p.z, __fmul_rn(lr, g.z));
+    p.w = __fsub_rn(p.w, __fmul_rn(lr, g.w));
+    ((float4*)var)[i] = p;
+  }
+  for (int64_t i = (n4 << 2) + first; i < n; i += stride)
+    var[i] = __fsub_rn(var[i], __fmul_rn(lr, grad[i]));
+}
+
 static int elementwise_grid(int64_t n) {
   int64_t blocks = (n + 1023) / 1024;
   if (blocks < 1) blocks = 1;
@@ -1090,6 +1110,17 @@ int dq_rmsprop_tf1(float* var, const float* grad, float* ms, float* mg, float* m
   hipLaunchKernelGGL(k_rmsprop, dim3(elementwise_grid(n)), dim3(256), 0, (hipStream_t)stream, var,
                      grad, ms, mg, mom, n, lr, decay, momentum, eps, centered);
   DQ_CHECK_LAUNCH("k_rmsprop");
+  return DQ_OK;
+}
+
+int dq_sgd_tf1(float* var, const float* grad, int64_t n, float lr, void* stream) {
+  DQ_CHECK_ARG(n >= 0, "bad arguments");
+  if (n == 0) return DQ_OK;      // (an empty tensor's pointer may be null)
+  DQ_CHECK_ARG(var && grad, "bad arguments");
+  const bool aligned = ((uintptr_t)var | (uintptr_t)grad) % 16 == 0;
+  hipLaunchKernelGGL(k_sgd, dim3(elementwise_grid(n)), dim3(256), 0, (hipStream_t)stream, var,
+                     grad, n, aligned ? n / 4 : (int64_t)0, lr);
+  DQ_CHECK_LAUNCH("k_sgd");
   return DQ_OK;
 }
 

@@ -49,6 +49,11 @@ cartpole_rainbow_network = gin_lite.register('gym_lib.cartpole_rainbow_network',
 acrobot_dqn_network = gin_lite.register('gym_lib.acrobot_dqn_network', networks.AcrobotDQNNetwork)
 acrobot_rainbow_network = gin_lite.register('gym_lib.acrobot_rainbow_network',
                                             networks.AcrobotRainbowNetwork)
+# the Fourier-basis networks (gym_lib.py:209-224, 276-292)
+cartpole_fourier_dqn_network = gin_lite.register('gym_lib.cartpole_fourier_dqn_network',
+                                                 networks.CartpoleFourierDQNNetwork)
+acrobot_fourier_dqn_network = gin_lite.register('gym_lib.acrobot_fourier_dqn_network',
+                                                networks.AcrobotFourierDQNNetwork)
 
 
 class Discrete(object):

@@ -29,7 +29,8 @@ from dopamine_amd import gin_lite
 from dopamine_amd.agents import networks
 from dopamine_amd.agents.dqn import dqn_agent
 from dopamine_amd.agents.implicit_quantile import implicit_quantile_agent
-from dopamine_amd.agents.optimizers import AdamOptimizer, RMSPropOptimizer
+from dopamine_amd.agents.optimizers import (AdamOptimizer, GradientDescentOptimizer,
+                                            RMSPropOptimizer)
 from dopamine_amd.agents.rainbow import rainbow_agent
 from dopamine_amd.discrete_domains import gym_lib  # noqa: F401 -- registers gym refs/constants
 from dopamine_amd.utils import checkpointer
@@ -43,6 +44,9 @@ gin_lite.register('tf.train.AdamOptimizer',
                   lambda: AdamOptimizer(**gin_lite.query('tf.train.AdamOptimizer')))
 gin_lite.register('tf.train.RMSPropOptimizer',
                   lambda: RMSPropOptimizer(**gin_lite.query('tf.train.RMSPropOptimizer')))
+gin_lite.register('tf.train.GradientDescentOptimizer',
+                  lambda: GradientDescentOptimizer(
+                      **gin_lite.query('tf.train.GradientDescentOptimizer')))
 gin_lite.register('atari_lib.nature_dqn_network', networks.NatureDQNNetwork)
 gin_lite.register('atari_lib.rainbow_network', networks.RainbowNetwork)
 gin_lite.register('atari_lib.implicit_quantile_network', networks.ImplicitQuantileNetwork)

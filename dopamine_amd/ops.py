@@ -223,6 +223,21 @@ class TF1RMSProp(object):
               int(self.centered), _stream(self.params))
 
 
+class TF1GradientDescent(object):
+  """tf.train.GradientDescentOptimizer over one flat fp32 buffer: var -= lr * grad, the
+  product rounded, then the difference.  It keeps no state."""
+
+  supports_multi = False
+
+  def __init__(self, params, learning_rate):
+    self.params = params
+    self.lr = float(learning_rate)
+
+  def step(self, grad, slot=None):
+    _lib.call('dq_sgd_tf1', p(self.params), p(_c(grad, torch.float32)), self.params.numel(),
+              self.lr, _stream(self.params))
+
+
 def sync_copy(dst, src):
   """Online -> target copy (dqn_agent.py:324-339)."""
   assert dst.numel() == src.numel() and dst.dtype == src.dtype

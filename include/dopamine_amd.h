@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define DQ_ABI_VERSION 10
+#define DQ_ABI_VERSION 11
 
 /* host-side return codes */
 #define DQ_OK 0
@@ -355,6 +355,10 @@ int dq_rmsprop_tf1(float* var, const float* grad, float* ms, float* mg, float* m
                    float lr, float decay, float momentum, float eps, int32_t centered,
                    void* stream);
 
+/* tf.train.GradientDescentOptimizer (dqn_acrobot.gin): var <- var - lr * grad, the product
+   rounded to float32, then the difference.  No state.  n = 0 launches nothing. */
+int dq_sgd_tf1(float* var, const float* grad, int64_t n, float lr, void* stream);
+
 /* ---------------- Nature-CNN (atari_lib.py:85-144) on fp32 MFMA ----------------
  * Input x: (B, 84, 84, 4) NHWC float32 (the gather's DQ_LAYOUT_F32_NHWC).  Weights
  * are views into the flat parameter buffer: conv (out, kh, kw, in), FC (out, in).
@@ -574,6 +578,44 @@ int dq_mlp_backward(const dq_mlp_params* p, const dq_mlp_params* g, int32_t batc
 int dq_mlp_backward_layer(const dq_mlp_params* p, const dq_mlp_params* g, int32_t batch,
                           const dq_mlp_acts* a, const float* dout, dq_mlp_acts* d, float* ws,
                           int32_t layer, int32_t part, void* stream);
+
+/* ---------------- Fourier-basis Q-network (gym_lib.py:135-206) ----------------
+ * FourierBasis + fourier_dqn_network: the observation scaled to [0, 1] (no clipping),
+ * F = (order + 1)^D - 1 features cos(float32(pi) * sum_d m[f][d] s[d]) and a bias-free linear
+ * head W (n_out, F), the only parameter.  Feature f's multipliers are the digits of f + 1 in
+ * base order + 1, dimension 0 the most significant (itertools.product without its first,
+ * all-zero tuple).  fp32 throughout, one launch forward, one backward. */
+#define DQ_FOURIER_MAX_IN 16
+#define DQ_FOURIER_MAX_OUT 64
+#define DQ_FOURIER_MAX_FEATURES 16383
+typedef struct dq_fourier_params { /* gym_lib.py:135-206 */
+  int32_t in_dim;                 /* D: observation floats (gym_lib.py:197) */
+  int32_t order;                  /* fourier_basis_order (gym_lib.py:177) */
+  int32_t n_out;                  /* num_actions (gym_lib.py:204-205) */
+  int32_t pad_;
+  float* w;                       /* (n_out, F), no bias (biases_initializer=None) */
+  float in_min[16];               /* float32(min_vals)             (gym_lib.py:159-164) */
+  float in_range[16];             /* float32(max_vals - min_vals), subtracted in float64 */
+} dq_fourier_params;
+typedef struct dq_fourier_acts {  /* gym_lib.py:166-169, 204-205 */
+  float* s;                       /* (B, D) the scaled input, or NULL */
+  float* phi;                     /* (B, F) the features, or NULL (the backward needs them) */
+  float* out;                     /* (B, n_out) */
+} dq_fourier_acts;
+/* F = (order + 1)^in_dim - 1 (gym_lib.py:153-157), or 0 if the shape is refused: in_dim
+   outside 1..16, order < 1, or F > DQ_FOURIER_MAX_FEATURES. */
+int dq_fourier_features(int32_t in_dim, int32_t order);
+/* forward (gym_lib.py:159-169, 192-206): x (B, D) float64 (x_is_f64) or float32, cast to
+   float32; s = (x - in_min) / in_range, correctly rounded; z = sum over d, in d order, of
+   m[f][d] * s[d]; phi = cosf(float32(pi) * z); out = phi W^T, each block's 256 partial sums
+   per output combined in one fixed order.  acts->s and acts->phi are stored when non-null. */
+int dq_fourier_forward(const dq_fourier_params* p, int32_t batch, const void* x, int32_t x_is_f64,
+                       dq_fourier_acts* acts, void* stream);
+/* backward (gym_lib.py:204-205, the head's weight gradient; nothing else is trained):
+   g->w (n_out, F) = dout^T phi with phi = acts->phi of the forward, every element by a plain
+   store, one summation order. */
+int dq_fourier_backward(const dq_fourier_params* p, const dq_fourier_params* g, int32_t batch,
+                        const dq_fourier_acts* acts, const float* dout, void* stream);
 
 /* ImplicitQuantileNetwork's quantile head (atari_lib.py:147-199) on the fp32 matrix cores.
    R = nq * batch rows ordered q * batch + b (tf.tile, atari_lib.py:174). */

@@ -14,6 +14,8 @@ each window:
 Prints every round, then per loop the medians, the spread (max - min) of each arm, the
 smallest HIP / PyTorch pair ratio and the A/A difference.
     python tools/gym_mlp_ab.py [--rounds 7] [--configs rainbow_cartpole dqn_cartpole]
+--configs also takes dqn_acrobot (the 24-24 MLP with plain gradient descent) and
+dqn_acrobot_fourier / dqn_cartpole_fourier (the Fourier-basis networks on fourier.hip).
 --profile-arm runs 300 learner steps and 300 agent steps of the HIP arm only (the run to put
 under a kernel-trace profiler for the per-launch table)."""
 import argparse
@@ -36,6 +38,10 @@ _AGENTS = os.path.join(ROOT, 'dopamine_amd', 'agents')
 CONFIGS = {'rainbow_cartpole': (os.path.join(_AGENTS, 'rainbow', 'configs', 'rainbow_cartpole.gin'),
                                 'RainbowAgent'),
            'dqn_cartpole': (os.path.join(_AGENTS, 'dqn', 'configs', 'dqn_cartpole.gin'), 'DQNAgent')}
+# (measured when named with --configs)
+for _n in ('dqn_acrobot', 'dqn_acrobot_fourier', 'dqn_cartpole_fourier'):
+  CONFIGS[_n] = (os.path.join(_AGENTS, 'dqn', 'configs', _n + '.gin'), 'DQNAgent')
+DEFAULT_CONFIGS = ['rainbow_cartpole', 'dqn_cartpole']
 
 
 def build(config, hip):
@@ -110,7 +116,7 @@ def summarize(name, rows):
 def main():
   ap = argparse.ArgumentParser()
   ap.add_argument('--rounds', type=int, default=7)
-  ap.add_argument('--configs', nargs='*', default=list(CONFIGS))
+  ap.add_argument('--configs', nargs='*', default=DEFAULT_CONFIGS)
   ap.add_argument('--window', type=float, default=0.3, help='seconds per learner window, at least')
   ap.add_argument('--agent-steps', type=int, default=2000)
   ap.add_argument('--profile-arm', action='store_true')
