@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from oracle.nature_cnn import (COND_FLOOR, LAYER_TOL, assert_guard_untouched,  # noqa: F401
-                               assert_layer_close, assert_spare_untouched, cond_ratio)
+                               assert_layer_close, assert_spare_untouched, bf16_round, cond_ratio)
 
 F, H = 7744, 512
 HEAD = ('emb_w', 'emb_b', 'fc1_w', 'fc1_b', 'fc2_w', 'fc2_b')
@@ -27,6 +27,10 @@ STAGES = ('cos', 'emb', 'h', 'q', 'dh', 'dw2', 'db2', 'dpre', 'dtl', 'dstate', '
 # deliberately wrong restatements head_reference can make (a test holds a correct result to
 # them and expects the assertion to fail)
 WRONG = ('state_row_b_major', 'drop_last_q')
+# the stages that are one GEMM (or one column of one: db1 and dbe are the products with the
+# ones column of dW1's and the wide dWe's second operand), whose operands head_reference can
+# round to bf16
+GEMM_STAGES = ('emb', 'h', 'q', 'dh', 'dw2', 'db2', 'dw1', 'db1', 'dwe', 'dbe')
 
 # (B, nq, A, E), the smallest shapes that reach each path of iqn.hip (fuse_tile = nq | 128):
 #   (1, 1, 1, 64)     R = 1: one-term reductions, one split-K slab everywhere, fused, nq = 1
@@ -104,13 +108,17 @@ def _lin(x, w, b):
   return x @ w.T + b
 
 
-def head_reference(B, nq, state, taus, params, dq, dev, wrong=()):
+def head_reference(B, nq, state, taus, params, dq, dev, wrong=(), bf16_stages=()):
   """float64 forward and backward of the head, stage by stage.
 
   state (B, 7744), taus (R,), dq (R, A) = d loss / d q; params: the six head tensors by name
   (HEAD; weights (out, in)); dev: the caller's cos (R, E), emb (R, 7744), h (R, 512), dh
   (R, 512) and dpre (R, 7744) -- the inputs of the stages that follow them.  wrong: names from
-  WRONG, a deliberately wrong restatement.
+  WRONG, a deliberately wrong restatement.  bf16_stages: the stages among GEMM_STAGES whose two
+  GEMM operands are rounded once to bf16 (bf16_round) before the float64 arithmetic and in
+  the stage's Σ|terms| -- exact products of rounded operands, what a GEMM on the bf16 matrix
+  instruction computes; biases and masks are never rounded.  For h the operand x is the fp32
+  Hadamard product first, then rounded.
 
   Returns a dict of float64 tensors, each beside its Σ|terms| (suffix _abs), and ``x``:
     cos            cos64 of the float32 argument; terms = 1
@@ -126,7 +134,11 @@ def head_reference(B, nq, state, taus, params, dq, dev, wrong=()):
     dw1, db1       dhᵀ [x | 1]                               on dev dh and x
     dwe, dbe       dpreᵀ [cos | 1]                           on dev dpre, dev cos."""
   assert set(wrong) <= set(WRONG), wrong
+  assert set(bf16_stages) <= set(GEMM_STAGES), bf16_stages
   R = B * nq
+
+  def ops(stage, *ts):             # the stage's GEMM operands, rounded if the stage is bf16
+    return [bf16_round(t).double() if stage in bf16_stages else t for t in ts]
   p = {n: _f64(params[n]) for n in HEAD}
   E = p['emb_w'].shape[1]
   state64, dq = _f64(state), _f64(dq)
@@ -137,21 +149,27 @@ def head_reference(B, nq, state, taus, params, dq, dev, wrong=()):
   # ---- forward
   out['cos'] = torch.cos(cos_argument(taus, E).double())
   out['cos_abs'] = torch.ones_like(out['cos'])
-  out['emb'] = torch.relu(_lin(d['cos'], p['emb_w'], p['emb_b']))
-  out['emb_abs'] = _lin(d['cos'].abs(), p['emb_w'].abs(), p['emb_b'].abs())
+  a, w = ops('emb', d['cos'], p['emb_w'])
+  out['emb'] = torch.relu(_lin(a, w, p['emb_b']))
+  out['emb_abs'] = _lin(a.abs(), w.abs(), p['emb_b'].abs())
   x32 = _f32(state)[rows] * _f32(dev['emb'])            # one fp32 rounding per element
   out['x'] = x32
   x = x32.double()
-  out['h'] = torch.relu(_lin(x, p['fc1_w'], p['fc1_b']))
-  out['h_abs'] = _lin(x.abs(), p['fc1_w'].abs(), p['fc1_b'].abs())
-  out['q'] = _lin(d['h'], p['fc2_w'], p['fc2_b'])
-  out['q_abs'] = _lin(d['h'].abs(), p['fc2_w'].abs(), p['fc2_b'].abs())
+  a, w = ops('h', x, p['fc1_w'])
+  out['h'] = torch.relu(_lin(a, w, p['fc1_b']))
+  out['h_abs'] = _lin(a.abs(), w.abs(), p['fc1_b'].abs())
+  a, w = ops('q', d['h'], p['fc2_w'])
+  out['q'] = _lin(a, w, p['fc2_b'])
+  out['q_abs'] = _lin(a.abs(), w.abs(), p['fc2_b'].abs())
   # ---- backward
   hmask = (d['h'] > 0).double()
-  out['dh'] = (dq @ p['fc2_w']) * hmask
-  out['dh_abs'] = (dq.abs() @ p['fc2_w'].abs()) * hmask
-  out['dw2'], out['dw2_abs'] = dq.T @ d['h'], dq.abs().T @ d['h'].abs()
-  out['db2'], out['db2_abs'] = dq.sum(0), dq.abs().sum(0)
+  a, w = ops('dh', dq, p['fc2_w'])
+  out['dh'] = (a @ w) * hmask
+  out['dh_abs'] = (a.abs() @ w.abs()) * hmask
+  a, w = ops('dw2', dq, d['h'])
+  out['dw2'], out['dw2_abs'] = a.T @ w, a.abs().T @ w.abs()
+  a, = ops('db2', dq)
+  out['db2'], out['db2_abs'] = a.sum(0), a.abs().sum(0)
   dx, dx_abs = d['dh'] @ p['fc1_w'], d['dh'].abs() @ p['fc1_w'].abs()
   emask = (d['emb'] > 0).double()
   out['dpre'] = dx * state64[rows] * emask
@@ -165,10 +183,14 @@ def head_reference(B, nq, state, taus, params, dq, dev, wrong=()):
   zero = torch.zeros(B, F, dtype=torch.float64)
   out['dstate'] = zero.index_add(0, rows, out['dtl'] * keep) * smask
   out['dstate_abs'] = zero.index_add(0, rows, out['dtl_abs'] * keep) * smask
-  out['dw1'], out['dw1_abs'] = d['dh'].T @ x, d['dh'].abs().T @ x.abs()
-  out['db1'], out['db1_abs'] = d['dh'].sum(0), d['dh'].abs().sum(0)
-  out['dwe'], out['dwe_abs'] = d['dpre'].T @ d['cos'], d['dpre'].abs().T @ d['cos'].abs()
-  out['dbe'], out['dbe_abs'] = d['dpre'].sum(0), d['dpre'].abs().sum(0)
+  a, w = ops('dw1', d['dh'], x)
+  out['dw1'], out['dw1_abs'] = a.T @ w, a.abs().T @ w.abs()
+  a, = ops('db1', d['dh'])
+  out['db1'], out['db1_abs'] = a.sum(0), a.abs().sum(0)
+  a, w = ops('dwe', d['dpre'], d['cos'])
+  out['dwe'], out['dwe_abs'] = a.T @ w, a.abs().T @ w.abs()
+  a, = ops('dbe', d['dpre'])
+  out['dbe'], out['dbe_abs'] = a.sum(0), a.abs().sum(0)
   return out
 
 

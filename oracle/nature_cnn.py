@@ -299,7 +299,21 @@ def _f64(t):
   return torch.as_tensor(t).detach().to('cpu', torch.float64)
 
 
-def layer_reference(layer, x_in, w, b, dz, pad=None):
+def bf16_round(t):
+  """fp32 -> bf16 (round to nearest, ties to even) -> fp32, in integer arithmetic on the bit
+  pattern: what torch's ``.bfloat16()`` and the device's packed conversion do to a GEMM
+  operand.  NaN stays NaN, +-0 and +-inf stay themselves; the result is float32."""
+  t = torch.as_tensor(t).detach().to('cpu', torch.float32).contiguous()
+  bits = t.view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+  up = (bits + 0x7FFF + ((bits >> 16) & 1)) & 0xFFFF0000       # a carry runs into the exponent
+  up = torch.where(up >= 1 << 31, up - (1 << 32), up).to(torch.int32)
+  return torch.where(torch.isnan(t), t, up.view(torch.float32))
+
+
+ROUND_OPS = ('x', 'w', 'dz')
+
+
+def layer_reference(layer, x_in, w, b, dz, pad=None, round_ops=()):
   """float64 forward and backward of one layer.
 
   layer: one of LAYERS.  x_in: the layer's input as the device keeps it (NHWC for a
@@ -307,13 +321,20 @@ def layer_reference(layer, x_in, w, b, dz, pad=None):
   w, b: the weights in torch layout ((out, in, kh, kw) / (out, in)) and the bias.  dz: the
   gradient of the layer's pre-activation, in the layer's output layout.  pad: another
   (left, right, top, bottom) padding for a convolution (a deliberately wrong reference).
+  round_ops: the operands among ROUND_OPS rounded once to bf16 (bf16_round) before the float64
+  arithmetic -- the contract of a GEMM on the bf16 matrix instruction: exact products of
+  rounded operands.  The bias is never rounded, the ReLU decision stays that of the unrounded
+  input, and every Σ|terms| is taken over the rounded operands.
 
   Returns a dict of float64 tensors, each result beside its Σ|terms| (suffix _abs):
     z, z_abs      the pre-activation and Σ|w||in| + |b|, in the output layout (NHWC)
     dx, dx_abs    (Wᵀ dz) · (in > 0) and Σ|w||dz| (masked alike), in the input layout
     dw, dw_abs    the weight gradient and Σ|dz||in|, flat (out, kh, kw, in) / (out, in)
     db, db_abs    the bias gradient and Σ|dz|."""
-  x_in, w, b, dz = _f64(x_in), _f64(w), _f64(b), _f64(dz)
+  assert set(round_ops) <= set(ROUND_OPS), round_ops
+  rnd = lambda name, t: _f64(bf16_round(t) if name in round_ops else t)
+  positive = _f64(x_in) > 0
+  x_in, w, b, dz = rnd('x', x_in), rnd('w', w), _f64(b), rnd('dz', dz)
   B = x_in.shape[0]
   if layer in _CONVS:
     p, stride, ishape, oshape = _CONVS[layer]
@@ -343,7 +364,7 @@ def layer_reference(layer, x_in, w, b, dz, pad=None):
     z_abs = fn([x.abs()], w.abs(), b.abs())
   dx, dw = grads(x, w, g)
   dx_abs, dw_abs = grads(x.abs(), w.abs(), g.abs())
-  keep = (x > 0).to(torch.float64)
+  keep = to_in(positive).to(torch.float64)
   return dict(z=from_out(z), z_abs=from_out(z_abs),
               dx=from_in(dx * keep), dx_abs=from_in(dx_abs * keep),
               dw=flat_w(dw), dw_abs=flat_w(dw_abs), db=sum_b(g), db_abs=sum_b(g.abs()))
