@@ -157,7 +157,11 @@ class DQNAgent(object):
     # np.sum's order below 8 steps only: longer horizons take the schedule without riders
     self.ride_replay = ride_replay and update_horizon < 8
     self.fused_head = fused_head
-    self._graph_sets = {}          # pipe -> (graphs per parity, optimizer graphs per parity)
+    # captured graphs.  Key True / False (the pipelined / non-pipelined per-step family): per
+    # step parity, the list of the step's captured parts in issue order (_step_parts; None
+    # where a part is absent); a chunk key (_chunk_keys): that chunk's one graph
+    self._graph_sets = {}
+    self._replays = {}             # True / False -> per parity, those parts' replay methods
     self._graph_pool = None
     self._eager_steps = {True: 0, False: 0}
     self._last_train_add_count = -1
@@ -249,7 +253,7 @@ class DQNAgent(object):
       return
     if self._peer is not None:
       self._dp.barrier()
-    self._graph_sets = {}
+    self._graph_sets, self._replays = {}, {}
     self._graph_pool = None
     if self._peer is not None:
       self._peer.close()
@@ -649,7 +653,7 @@ class DQNAgent(object):
 
   def _prefetch(self, i):
     mem = self._replay.memory
-    if self._gather_plan is not None:   # capturing a chunk-gather graph (_run_gather_chunk)
+    if self._gather_plan is not None:   # capturing a chunk-gather graph (_run_train_ops_chunk)
       p, j = self._gather_plan
       if j == 0:                        # the chunk's K next batches: one sample + one gather
         mem.sample_device(self._batch_size, layout=self._replay._layout, out=self._cb_sets()[p],
@@ -729,15 +733,34 @@ class DQNAgent(object):
   def _split_allreduce(self):
     return self._collective() and self._hip is not None and not self._fused_opt()
 
-  def _split_parts(self, c, k, pipe):
-    """(head_a | None, head_b, tail, opt): the callables of step slot c, parity k, that
-    Exchange.split_step issues (each alone is what one of the step's graphs captures)."""
-    tail = lambda: self._grad_step_tail(c, k, pipe)
-    opt = lambda: self._device_opt_step(k)
-    if self._fused():
-      return (lambda: self._grad_step_head(c, k, pipe, 'a'),
-              lambda: self._grad_step_head(c, k, pipe, 'b'), tail, opt)
-    return None, lambda: self._grad_step_head(c, k, pipe), tail, opt
+  def _step_parts(self, c, k, pipe, slot):
+    """The ordered callables of the gradient step of slot c, parity k, under the schedule in
+    force (each alone is what one of the step's graphs captures; _issue runs them).  slot: the
+    step's trace slot.  Split all-reduce: (head_a | None, head_b, tail, opt), what
+    Exchange.split_step issues; a collective without the split: (gradient step, optimizer
+    step + trace copies); a single replica or the peer exchange: those two in one."""
+    if self._split_allreduce():
+      tail = lambda: self._grad_step_tail(c, k, pipe)
+      opt = lambda: self._device_opt_step(k)
+      if self._fused():
+        return (lambda: self._grad_step_head(c, k, pipe, 'a'),
+                lambda: self._grad_step_head(c, k, pipe, 'b'), tail, opt)
+      return None, lambda: self._grad_step_head(c, k, pipe), tail, opt
+    grad = lambda: self._grad_step(c, k, pipe)
+    opt = lambda: (self._device_opt_step(k), self._trace_step(slot, c))
+    return (grad, opt) if self._collective() else (lambda: (grad(), opt()),)
+
+  def _issue(self, parts, k):
+    """Runs a step's parts -- _step_parts' callables, or the replay methods of the graphs
+    that captured them (None where a part is absent) -- with what belongs between them."""
+    if len(parts) == 4:
+      self._split_step(parts, k)
+    elif len(parts) == 2:
+      parts[0]()
+      self._dp.allreduce_grads()
+      parts[1]()
+    else:
+      parts[0]()
 
   def _split_step(self, parts, k):
     self._dp.split_step(*parts, k=k, defer=self._defer_fc, branch_first=self.branch_first,
@@ -883,43 +906,6 @@ class DQNAgent(object):
         v.copy_(src[k])
     self._cb_ready = None
 
-  def _run_gather_chunk(self, K):
-    """K gradient steps as one chunk-gather graph replay (captured per starting parity,
-    three variants: entering from the per-call pipeline, and the two alternating sets)."""
-    mem = self._replay.memory
-    k0 = self._opt_steps % 2
-    steady = self._cb_ready is not None
-    p = 1 - self._cb_ready if steady else 0
-    key = ('gchunk', K, k0, p, steady)
-    if key not in self._graph_sets:
-      torch.cuda.synchronize(self._device)
-      self._cb_sets()
-      saved = list(self._pbuf)
-      try:
-        for st, q in ((False, 0), (True, 0), (True, 1)):
-          g = torch.cuda.CUDAGraph()
-          with torch.cuda.graph(g, pool=self._graph_pool):
-            for j in range(K):
-              k = (k0 + j) % 2
-              if j == 0:                # the prefetched batch
-                self._pbuf[k] = self._cbv[1 - q][K - 1] if st else saved[k0]
-              self._gather_plan = (q, j)
-              self._grad_step(k, k, True)
-              self._device_opt_step(k)
-              self._trace_step(j, k)
-            self._gather_plan = None
-          self._graph_pool = g.pool()
-          self._graph_sets[('gchunk', K, k0, q, st)] = g
-      finally:
-        self._gather_plan = None
-        self._pbuf[:] = saved
-    mem.reserve_rng(self._batch_size, steps=K)
-    self._graph_sets[key].replay()
-    self._opt_steps += K
-    self._cb_ready = p
-    # (the batch the chunk's last step trained on)
-    self._step_done(self._cbv[p][K - 2], (k0 + K) % 2, True)
-
   def _step_done(self, batch, slot, has_prefetch):
     """The host's books after a gradient step (or a chunk's last one) on ``batch``: the
     replay's last transition, the slot the next step reads, and whether its batch is
@@ -957,76 +943,42 @@ class DQNAgent(object):
       mem.reserve_rng(self._batch_size)
       self._prefetch(c)
     mem.reserve_rng(self._batch_size)
-    graphs = self._graph_sets.get(pipe)
-    if self._split_allreduce():
-      if graphs is not None:
-        self._split_step([None if g is None else g.replay for g in graphs[0][k]], k)
-      else:
-        self._split_step(self._split_parts(c, k, pipe), k)
-        self._eager_steps[pipe] += 1
-    elif graphs is not None:
-      graphs[0][k].replay()
-      if self._collective():
-        self._dp.allreduce_grads()
-        graphs[1][k].replay()
+    replays = self._replays.get(pipe)
+    if replays is not None:
+      self._issue(replays[k], k)
     else:
-      self._grad_step(c, k, pipe)
-      if self._collective():
-        self._dp.allreduce_grads()
-      self._device_opt_step(k)
-      self._trace_step(self._UNROLL + k, c)
+      self._issue(self._step_parts(c, k, pipe, self._UNROLL + k), k)
       self._eager_steps[pipe] += 1
     self._opt_steps += 1
     self._step_done(self._pbuf[c], 1 - c, pipe)
-    if graphs is None and self.use_hip_graph and self._eager_steps[pipe] >= 3:
+    if replays is None and self.use_hip_graph and self._eager_steps[pipe] >= 3:
       self._capture(pipe)
 
   @property
   def _graphs(self):
-    g = self._graph_sets.get(self.pipeline)
-    return None if g is None else g[0]
+    return self._graph_sets.get(self.pipeline)
+
+  def _record(self, fn, mode):
+    """fn() recorded (capture_error_mode ``mode``) into a new graph in the pool that all the
+    agent's graphs share -> the graph.  The caller synchronizes before its first one."""
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, pool=self._graph_pool, capture_error_mode=mode):
+      fn()
+    self._graph_pool = g.pool()
+    return g
 
   def _capture(self, pipe):
-    """Two graphs, one per gradient-step parity k (pipeline slot and Adam
-    beta-power slot both alternate with k); with one GPU the optimizer is in the
-    same graph, with N GPUs it is a second graph after the RCCL all-reduce."""
+    """A graph per part of the step (_step_parts) and gradient-step parity k (pipeline slot
+    and Adam beta-power slot both alternate with k): with one GPU a single graph, the
+    optimizer in it; with N GPUs the collectives run between the parts' graphs."""
     torch.cuda.synchronize(self._device)
-    graphs, graphs_opt, pool = [], [], self._graph_pool
-    if self._split_allreduce():
-      for k in (0, 1):
-        parts = []
-        for fn in self._split_parts(k, k, pipe):
-          gr = None
-          if fn is not None:
-            gr = torch.cuda.CUDAGraph()
-            # thread_local: torch's process-group watchdog thread polls the events of the
-            # collectives issued just before (global mode would fail its queries)
-            with torch.cuda.graph(gr, pool=pool, capture_error_mode='thread_local'):
-              fn()
-            pool = gr.pool()
-          parts.append(gr)
-        graphs.append(parts)
-      self._graph_pool = pool
-      self._graph_sets[pipe] = (graphs, [])
-      return
-    for k in (0, 1):
-      c = k
-      g = torch.cuda.CUDAGraph()
-      with torch.cuda.graph(g, pool=pool, capture_error_mode='thread_local'):
-        self._grad_step(c, k, pipe)
-        if not self._collective():
-          self._device_opt_step(k)
-          self._trace_step(self._UNROLL + k, c)
-      pool = g.pool()
-      graphs.append(g)
-      if self._collective():
-        go = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(go, pool=pool, capture_error_mode='thread_local'):
-          self._device_opt_step(k)
-        graphs_opt.append(go)
-    # capture records without executing: tape cursor and buffers are unchanged
-    self._graph_pool = pool
-    self._graph_sets[pipe] = (graphs, graphs_opt)
+    # thread_local: torch's process-group watchdog thread polls the events of the
+    # collectives issued just before (global mode would fail its queries).
+    # Capture records without executing: tape cursor and buffers are unchanged
+    graphs = [[None if fn is None else self._record(fn, 'thread_local')
+               for fn in self._step_parts(k, k, pipe, self._UNROLL + k)] for k in (0, 1)]
+    self._graph_sets[pipe] = graphs
+    self._replays[pipe] = [[None if g is None else g.replay for g in gs] for gs in graphs]
 
   def _sync_target(self):
     self._join_fc()
@@ -1230,16 +1182,27 @@ class DQNAgent(object):
       return True
     if self._graph_sets.get(True) is None:
       return False
-    if not self._chunks_apply():
-      return True
+    return not self._chunks_apply() or all(
+        key in self._graph_sets for k in (0, 1) for key in self._chunk_keys(self._UNROLL, k)[1])
+
+  def _chunk_keys(self, K, k0):
+    """(kind, keys, now): the keys in _graph_sets of every graph that a chunk of K steps from
+    parity k0 may replay under this configuration, and the one it replays as the agent stands.
+    'gather' (_chunk_gathers) -- ('gchunk', K, k0, set filled, steady): entering from the
+    per-call pipeline and the two alternating sets, captured together; 'peer' (several learners
+    on the peer exchange, whose chunk steps defer their all-gather) -- ('chunk', K, k0, pending):
+    without and with the predecessor's deferred gather (a learner-loop call of two chunks or
+    more captures the latter); None -- ('chunk', K, k0)."""
     if self._chunk_gathers():
-      return all(('gchunk', self._UNROLL, k, 0, False) in self._graph_sets for k in (0, 1))
-    if self._peer is not None and self._peer.world > 1 and self._fused():
-      # the chunk graphs with and without the predecessor's deferred gather (a learner-loop
-      # call of two chunks or more captures the latter)
-      return all(('chunk', self._UNROLL, k, p) in self._graph_sets for k in (0, 1)
-                 for p in (False, True))
-    return all(('chunk', self._UNROLL, k) in self._graph_sets for k in (0, 1))
+      steady = self._cb_ready is not None
+      kind, now = 'gather', (1 - self._cb_ready if steady else 0, steady)
+      variants = ((0, False), (0, True), (1, True))
+    elif self._peer is not None and self._peer.world > 1 and self._fused():
+      kind, now, variants = 'peer', (self._peer_pending,), ((False,), (True,))
+    else:
+      kind, now, variants = None, (), ((),)
+    name = 'gchunk' if kind == 'gather' else 'chunk'
+    return kind, [(name, K, k0) + v for v in variants], (name, K, k0) + now
 
   def _chunks_apply(self):
     """Chunk graphs: a single replica's or the peer exchange's pipelined HIP-CNN steps, or the
@@ -1265,51 +1228,56 @@ class DQNAgent(object):
     return not any(t % self.target_update_period == 0 for t in range(t0, last))
 
   def _run_train_ops_chunk(self, K):
-    """K pipelined gradient steps as one replay of a K-step graph (captured per
-    starting parity on first use)."""
-    if self._chunk_gathers():
-      return self._run_gather_chunk(K)
-    mem = self._replay.memory
+    """K pipelined gradient steps as one replay of a K-step graph (captured per starting
+    parity on first use; a chunk gather's three variants together: _chunk_keys)."""
     k0 = self._opt_steps % 2
-    defer = (not self._collective() and self._peer is not None and self._peer.world > 1 and
-             self._fused())
-    pending = defer and self._peer_pending
-    key = ('chunk', K, k0) + ((pending,) if defer else ())
-    g = self._graph_sets.get(key)
+    kind, keys, key = self._chunk_keys(K, k0)
+    gather, defer = kind == 'gather', kind == 'peer'
     self._join_fc()                   # (a capture: nothing outside it may be pending)
-    if g is None:
+    if key not in self._graph_sets:
       torch.cuda.synchronize(self._device)
-      g = torch.cuda.CUDAGraph()
-      if not self._collective():
-        try:
-          with torch.cuda.graph(g, pool=self._graph_pool):
-            for j in range(K):
-              k = (k0 + j) % 2
-              self._peer_fwd_ag, self._peer_defer_ag = defer and (j > 0 or pending), defer
-              self._grad_step(k, k, True)
-              self._device_opt_step(k)
-              self._trace_step(j, k)
-        finally:
-          self._peer_fwd_ag = self._peer_defer_ag = False
-      else:
-        # N > 1: each step's split schedule with its RCCL all-reduces captured (the comm
-        # stream and RCCL's own streams fork from and join back into the capture; each
-        # step's fc all-reduce + update is joined in the next step, the last one at the
-        # end of the chunk).  thread_local: the process group's watchdog thread keeps
-        # querying its events while this thread captures.
-        with torch.cuda.graph(g, pool=self._graph_pool, capture_error_mode='thread_local'):
-          for j in range(K):
-            k = (k0 + j) % 2
-            self._split_step(self._split_parts(k, k, True), k)
-          self._join_fc()
-      self._graph_pool = g.pool()
-      self._graph_sets[key] = g
-    mem.reserve_rng(self._batch_size, steps=K)
-    g.replay()
-    self._peer_pending = defer        # the last step's gather is left to the next chunk / flush
+      if gather:
+        self._cb_sets()
+      saved = list(self._pbuf)
+
+      def gather_step(j, k, q, steady):     # step j of a chunk that fills set q
+        if j == 0:                          # the prefetched batch
+          self._pbuf[k] = self._cbv[1 - q][K - 1] if steady else saved[k0]
+        self._gather_plan = (q, j)
+
+      def peer_step(j, k, pending=False):   # (changes nothing unless the steps defer)
+        self._peer_fwd_ag, self._peer_defer_ag = defer and (j > 0 or pending), defer
+
+      def steps(variant):
+        for j in range(K):
+          k = (k0 + j) % 2
+          (gather_step if gather else peer_step)(j, k, *variant)
+          self._issue(self._step_parts(k, k, True, j), k)
+        self._join_fc()               # (the collective chunk's last fc exchange)
+      # N > 1 (collective): each step's split schedule with its RCCL all-reduces captured (the
+      # comm stream and RCCL's own streams fork from and join back into the capture; each
+      # step's fc all-reduce + update is joined in the next step, the last one at the end of
+      # the chunk).  thread_local: the process group's watchdog thread keeps querying its
+      # events while this thread captures.
+      mode = 'thread_local' if self._collective() else 'global'
+      try:
+        for new in keys if gather else (key,):
+          self._graph_sets[new] = self._record(lambda: steps(new[3:]), mode)
+      finally:
+        self._gather_plan = None
+        self._peer_fwd_ag = self._peer_defer_ag = False
+        self._pbuf[:] = saved         # (the chunk gather's substitutions)
+    self._replay.memory.reserve_rng(self._batch_size, steps=K)
+    self._graph_sets[key].replay()
     self._opt_steps += K
     c = (k0 + K - 1) % 2
-    self._step_done(self._pbuf[c], 1 - c, True)
+    batch = self._pbuf[c]             # the batch the chunk's last step trained on
+    if gather:
+      self._cb_ready = key[3]         # (the set this chunk filled)
+      batch = self._cbv[key[3]][K - 2]
+    else:
+      self._peer_pending = defer      # the last step's gather is left to the next chunk / flush
+    self._step_done(batch, 1 - c, True)
 
   def _train_step(self):
     """dqn_agent.py:418-442."""

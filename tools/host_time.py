@@ -54,10 +54,12 @@ def main():
   g = agent._graphs
   if g is None:
     return
+  # per parity, the replay methods of the step's captured parts (one graph for this agent)
+  replays = [[None if p is None else p.replay for p in parts] for parts in g]
   torch.cuda.synchronize()
   t0 = time.perf_counter()
   for i in range(K):
-    g[i % 2].replay()
+    agent._issue(replays[i % 2], i % 2)
   t1 = time.perf_counter()
   torch.cuda.synchronize()
   t2 = time.perf_counter()
@@ -65,12 +67,12 @@ def main():
   # the same steps with S consecutive steps captured in ONE graph: the graph
   # boundary's cost per step (what a multi-step learner graph would save)
   for S in (2, 4, 8):
-    gs = torch.cuda.CUDAGraph()
-    torch.cuda.synchronize()
-    with torch.cuda.graph(gs, pool=agent._graph_pool):
+    def steps():
       for j in range(S):
         agent._grad_step(j % 2, j % 2, True)
         agent._device_opt_step(j % 2)
+    torch.cuda.synchronize()
+    gs = agent._record(steps, 'global')
     torch.cuda.synchronize()
     n = K // S
     t0 = time.perf_counter()
