@@ -96,7 +96,8 @@ class DQNAgent(object):
                process_group=None,
                shard_optimizer=False,
                native_comm=True,
-               exchange='collective'):
+               exchange='collective',
+               double_dqn=False):
     assert num_actions is not None
     assert isinstance(observation_shape, tuple)      # abstract_agent.py:34
     self.num_actions = num_actions
@@ -140,6 +141,17 @@ class DQNAgent(object):
     if exchange not in ('collective', 'peer'):
       raise ValueError("exchange must be 'collective' or 'peer'")
     self.exchange = exchange
+    # Double DQN (implicit_quantile_agent.py:183-188's rule for DQN and C51): the greedy next
+    # action comes from the ONLINE network on s' at this step's parameters, the target
+    # network evaluates it.  The online network's second forward runs inside the step
+    # (_online_loss), never in the prefetch beside the previous step's update.
+    self.double_dqn = double_dqn
+    if self._double() and process_group is not None:
+      # the peer exchange defers part of the parameter all-gather into the next forward; what
+      # the second online forward would read there is not designed
+      raise ValueError('double_dqn is not supported with data-parallel learners '
+                       '(process_group)')
+    self._online_next = None       # double_dqn: the online network's forward-only executor on s'
     self._peer = None
     self._dp = None                # N > 1: the collective exchange (data_parallel.Exchange)
     self._defer_fc = False         # set by train_gradient_steps (learner-only loop)
@@ -305,6 +317,8 @@ class DQNAgent(object):
     elif getattr(self, '_last_online_out', None) is not None and 'q' in (self._ptgt[c] or {}):
       d['online_out'] = self._last_online_out       # the PyTorch-network path (e.g. CartPole)
       d['target_out'] = self._ptgt[c]['q']
+    if self._double():               # the online network's output on next_state (select)
+      d['online_next_out'] = self._last_online_next.reshape(self._batch_size, -1)
     return d
 
   def _trace_step(self, slot, c):
@@ -357,6 +371,33 @@ class DQNAgent(object):
     return dict(online=self._mlp_executor(self.online_convnet, B, True),
                 target=[self._mlp_executor(self.target_convnet, B, False) for _ in range(2)])
 
+  # double_dqn is this class's to carry out (the executor, the loss entry, the schedule);
+  # ImplicitQuantileAgent, which has its own double-DQN path, turns it off
+  _base_double_dqn = True
+
+  def _double(self):
+    return bool(self.double_dqn) and self._base_double_dqn
+
+  def _build_online_next(self):
+    """double_dqn: the forward-only executor of the online network on next_state (it reads the
+    online parameters in place), or None on the PyTorch paths.  A hook: a subclass with a
+    double-DQN path of its own builds nothing here."""
+    B = self._batch_size
+    if self._hip is not None:
+      from dopamine_amd.cnn import HipNatureCNN
+      return HipNatureCNN(self.online_convnet, B)
+    if self._mlp is not None:
+      return self._mlp_executor(self.online_convnet, B, False)
+    return None
+
+  def _online_next_forward(self, x):
+    """The online network's output on next_state at the parameters as they stand on the
+    step's stream (no gradient)."""
+    if self._online_next is not None:
+      return self._online_next.forward(x)
+    with torch.no_grad():
+      return self.online_convnet(self._state_input(x))
+
   def _build_networks(self):
     self.online_convnet = self._make_network(self._seed)
     self.target_convnet = self._make_network(self._seed + 1)
@@ -370,6 +411,8 @@ class DQNAgent(object):
       B = self._batch_size
       self._hip = dict(online=HipNatureCNN(self.online_convnet, B),
                        target=[HipNatureCNN(self.target_convnet, B) for _ in range(2)])
+    if self._double():
+      self._online_next = self._build_online_next()
 
   def _online_forward(self, x):
     """Online network output for the loss (keeps what the backward needs)."""
@@ -414,8 +457,20 @@ class DQNAgent(object):
     q = self._online_forward(t['state'])
     self._last_online_out = q.detach()
     out = ops.dqn_huber_loss(q.detach(), tgt['q'], t['action'], t['reward'], t['terminal'],
-                             self.cumulative_gamma, out=self._loss_out)
+                             self.cumulative_gamma, out=self._loss_out,
+                             select_q=self._select_output(t))
     return q, out['grad']
+
+  def _select_output(self, t):
+    """double_dqn: the online network's output on next_state, computed here -- in the step, on
+    its stream, after the online forward on s and before the loss kernel -- so it reads the
+    parameters every earlier update has finished with and this step's has not touched.  (The
+    prefetch runs beside the previous step's backward and, with the fused optimizer, its
+    update: a forward there would read stale or half-updated parameters.)  None otherwise."""
+    if not self._double():
+      return None
+    self._last_online_next = self._online_next_forward(t['next_state']).detach()
+    return self._last_online_next
 
   def _fused_opt(self):
     """fuse_optimizer + single replica + HIP CNN + TF1 Adam or RMSProp: the optimizer
@@ -497,8 +552,10 @@ class DQNAgent(object):
     """fused_head: the loss kernel consumes the CNN's fc2 k-band partials and writes
     fc2's input gradient (cnn.forward_fused + _fused_loss), so the forward and the
     backward each lose a launch (the Nature-CNN agents: DQN's Huber here, Rainbow's C51
-    in its subclass)."""
-    return self.fused_head and self._rides()
+    in its subclass).  Not with double_dqn: the fused loss kernels have no input for the
+    online network's output on s', so that agent takes fused_head=False's schedule (stored
+    outputs, then the plain loss entry)."""
+    return self.fused_head and self._rides() and not self._double()
 
   def _fused_loss(self, t, c):
     """_online_loss on the CNN's fc2 partials: Q / Q' summed in the loss kernel

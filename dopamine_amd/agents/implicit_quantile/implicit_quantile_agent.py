@@ -41,13 +41,19 @@ class ImplicitQuantileAgent(rainbow_agent.RainbowAgent):
     self.num_tau_prime_samples = num_tau_prime_samples
     self.num_quantile_samples = num_quantile_samples
     self.quantile_embedding_dim = quantile_embedding_dim
-    self.double_dqn = double_dqn
     kwargs.setdefault('optimizer', AdamOptimizer(learning_rate=0.00025, epsilon=0.0003125))
     super().__init__(sess=sess, num_actions=num_actions, network=network,
                      summary_writer=summary_writer,
-                     summary_writing_frequency=summary_writing_frequency, **kwargs)
+                     summary_writing_frequency=summary_writing_frequency,
+                     double_dqn=double_dqn, **kwargs)
 
   _loss_name = 'QuantileLoss'
+  # double_dqn is carried out here (_target_forward / _online_loss and the executors below),
+  # not by DQNAgent's select forward and loss entries
+  _base_double_dqn = False
+
+  def _build_online_next(self):
+    return None
   # the act path's Q-values draw taus from the device counter, so evaluating them on every
   # action (the device epsilon-greedy does) would move the tau stream: host draws here
   device_egreedy = False

@@ -156,10 +156,13 @@ class RainbowAgent(dqn_agent.DQNAgent):
     """rainbow_agent.py:200-305."""
     logits = self._online_forward(t['state']).view(-1, self.num_actions, self._num_atoms)
     prioritized = self._replay_scheme == 'prioritized'
+    select = self._select_output(t)       # double_dqn: the online logits on s' (else None)
+    if select is not None:
+      select = select.view(-1, self.num_actions, self._num_atoms)
     out = ops.c51_loss(logits.detach(), tgt['logits'], t['action'], t['reward'], t['terminal'],
                        self._support, self.cumulative_gamma,
                        probs=t['sampling_probabilities'] if prioritized else None,
-                       out=self._loss_out)
+                       out=self._loss_out, select_logits=select)
     return logits, out['grad']
 
   # The C51 loss split in two (head_from 8): the target half (softmax, Q, greedy action,

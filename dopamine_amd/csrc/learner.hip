@@ -563,6 +563,172 @@ __global__ __launch_bounds__(kC51WideT) void k_c51_wide(C51Args a) {
   }
 }
 
+// ---------------------------------------------------------------------------
+// Double-DQN C51 (stored logits, 2..256 atoms): the greedy next action is the first argmax
+// of the SELECT logits' Q (the online network on s'), the target distribution the softmax of
+// the TARGET logits' row a* (implicit_quantile_agent.py:183-188's rule on rb:200-251).  With
+// select == target every output is bitwise k_c51's (N <= 64) and k_c51_wide's (N > 64): the
+// row arithmetic is c51_dev.h's WideRow pieces, which at one chunk are k_c51's operations,
+// and the projection is the full j-ordered sum both kernels' sums equal bit for bit.
+// One 256-thread block per sample b, as k_c51_wide:
+//   before the barrier  wave w takes actions w, w + 4, ..: it loads the select row and the
+//                       raw target row of an action together, forms the select row's softmax
+//                       and Q, and keeps the raw target row of its own first-max action in
+//                       registers (the block's a* is the first max of one of the four waves).
+//                       After its last action it forms that one row's softmax into its slot
+//                       of s_pt -- four candidate rows side by side, one of them a*'s -- so
+//                       no global load and no softmax follow the barrier.  Only Q[A] and the
+//                       four candidates live in LDS, not an [A][N] table.  The rest (last
+//                       wave: the chosen online row; clip(Tz); zeros; probability minimum)
+//                       is k_c51_wide's.
+//   after it            every thread scans Q[A] for a* (first max), reads candidate a* % 4
+//                       and goes on as k_c51_wide.
+// Fixed-order reductions only, no atomics, nothing outside the block.
+// ---------------------------------------------------------------------------
+// dynamic LDS floats: [4][N] candidate target probabilities, [A] select Q, [N] clip(Tz),
+// [N] sh, [N] online p, 4 loss partials + 4 probability minima + lse
+__host__ __device__ constexpr int c51_double_floats(int A, int N) {
+  return kC51WideWaves * N + A + 3 * N + 12;
+}
+
+template <bool kProbs>
+__global__ __launch_bounds__(kC51WideT) void k_c51_double(C51Args a, const float* __restrict__ sl) {
+  warm_kernargs<sizeof(C51Args) + 8>();
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int N = a.N, A = a.A, b = blockIdx.x, t = threadIdx.x;
+  const int lane = t & 63, wave = t >> 6, nch = (N + kWave - 1) >> 6;
+  float* s_pt = smem;                        // [4][N] wave w's candidate target probabilities
+  float* s_q = s_pt + kC51WideWaves * N;     // [A]    select Q
+  float* s_tz = s_q + A;                     // [N]    clip(Tz_j)
+  float* s_sh = s_tz + N;                    // [N]    chosen online row, y_i - max y
+  float* s_py = s_sh + N;                    // [N]    chosen online row, softmax
+  float* s_red = s_py + N;                   // [0..3] loss partials, [4..7] min probs, [8] lse
+  const bool on = t < N;
+  const float ninf = -__builtin_inff();
+  const float z = a.support[min(t, N - 1)];
+  const int ab = a.act[b];
+  const float rew_b = a.rew[b], term_b = (float)a.term[b];
+  const float vmin = a.support[0], vmax = a.support[N - 1], z1 = a.support[1];
+  const float pr_b = kProbs ? a.probs[b] : 0.0f;
+  const float dz = __fsub_rn(z1, vmin);
+  // the chosen online row (last wave) and each wave's first select / target rows: issued
+  // with the scalars above, ahead of any use
+  const int64_t base = (int64_t)b * A * N;
+  const int a0 = min(wave, A - 1);
+  WideRow xs = wide_load(sl + base + (int64_t)a0 * N, N, lane, ninf);
+  WideRow xt = wide_load(a.tl + base + (int64_t)a0 * N, N, lane, ninf);
+  WideRow y = xs;
+  if (wave == kC51WideWaves - 1) y = wide_load(a.ol + base + (int64_t)ab * N, N, lane, ninf);
+  {
+    const float gt = __fmul_rn(a.cg, __fsub_rn(1.0f, term_b));
+    if (on) s_tz[t] = fminf(fmaxf(__fadd_rn(rew_b, __fmul_rn(gt, z)), vmin), vmax);
+  }
+  if (kProbs) {   // PER: the minimum over all B probabilities (k_c51's weight, rb:277-280)
+    float pm = a.probs[min(t, a.B - 1)];
+    for (int i = t + kC51WideT; i < a.B; i += kC51WideT) pm = fminf(pm, a.probs[i]);
+    pm = fast_min(pm);
+    if (lane == 0) s_red[4 + wave] = pm;
+  }
+  WideRow zc;       // the support at this lane's atoms
+#pragma unroll
+  for (int c = 0; c < kC51WideChunks; ++c) zc.v[c] = a.support[min(lane + c * kWave, N - 1)];
+  WideRow bt = xt;  // raw target row of this wave's first-max select action
+  float bq = 0.0f;
+  for (int act = wave; act < A; act += kC51WideWaves) {
+    // the next action's two rows, in flight under this one's softmax (clamped: in bounds)
+    const int nx = min(act + kC51WideWaves, A - 1);
+    const WideRow ns = wide_load(sl + base + (int64_t)nx * N, N, lane, ninf);
+    const WideRow nt = wide_load(a.tl + base + (int64_t)nx * N, N, lane, ninf);
+    WideRow sh, e, zp;
+    const float s = wide_softmax_terms(xs, N, nch, lane, sh, e);
+#pragma unroll
+    for (int c = 0; c < kC51WideChunks; ++c) {
+      const float p = __fdiv_rn(e.v[c], s);
+      zp.v[c] = lane + c * kWave < N ? __fmul_rn(zc.v[c], p) : 0.0f;
+    }
+    const float q = wide_sum(zp, nch);
+    if (lane == 0) s_q[act] = q;
+    if (act == wave || q > bq) {   // first max within the wave's actions (strict >)
+      bq = q;
+      bt = xt;
+    }
+    xs = ns;
+    xt = nt;
+  }
+  if (wave < A) {   // this wave's candidate: softmax of the kept target row
+    WideRow sh, e;
+    const float s = wide_softmax_terms(bt, N, nch, lane, sh, e);
+#pragma unroll
+    for (int c = 0; c < kC51WideChunks; ++c) {
+      const int i = lane + c * kWave;
+      if (i < N) s_pt[wave * N + i] = __fdiv_rn(e.v[c], s);
+    }
+  }
+  if (wave == kC51WideWaves - 1) {
+    WideRow sh, ey;
+    const float sy = wide_softmax_terms(y, N, nch, lane, sh, ey);
+#pragma unroll
+    for (int c = 0; c < kC51WideChunks; ++c) {
+      const int i = lane + c * kWave;
+      if (i < N) {
+        s_sh[i] = sh.v[c];
+        s_py[i] = __fdiv_rn(ey.v[c], sy);
+      }
+    }
+    if (lane == 0) s_red[8] = logf(sy);
+  }
+  // grad_logits is fully written: zeros on the rows not chosen
+  {
+    float* g = a.grad + base;
+    for (int act = 0; act < A; ++act)
+      if (act != ab && on) g[act * N + t] = 0.0f;
+  }
+  __syncthreads();   // s_pt, s_q, s_tz, s_sh, s_py, s_red[4..8] complete
+  float w = 1.0f;
+  if (kProbs) {
+    const float pm = fminf(fminf(s_red[4], s_red[5]), fminf(s_red[6], s_red[7]));
+    const float m = __fdiv_rn(1.0f, sqrt_rn(__fadd_rn(pm, 1e-10f)));
+    w = __fdiv_rn(__fdiv_rn(1.0f, sqrt_rn(__fadd_rn(pr_b, 1e-10f))), m);
+  }
+  const float gscale = __fmul_rn(w, __fdiv_rn(1.0f, (float)a.B));
+  int astar = 0;     // greedy select action, first max
+  {
+    float best = s_q[0];
+    for (int act = 1; act < A; ++act) {
+      const float qa = s_q[act];
+      if (qa > best) {
+        best = qa;
+        astar = act;
+      }
+    }
+  }
+  const float* pst = s_pt + (astar & (kC51WideWaves - 1)) * N;
+  float term = 0.0f;
+  if (on) {
+    float proj = 0.0f;               // sum_j c(i, j) p_j in j order (rb:340-494)
+    int j = 0;
+    for (; j + 8 <= N; j += 8) {     // 8 terms' LDS reads in flight, then summed in order
+      float tt[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) tt[u] = __fmul_rn(c51_quot(s_tz[j + u], z, dz), pst[j + u]);
+#pragma unroll
+      for (int u = 0; u < 8; ++u) proj = __fadd_rn(proj, tt[u]);
+    }
+    for (; j < N; ++j) proj = __fadd_rn(proj, __fmul_rn(c51_quot(s_tz[j], z, dz), pst[j]));
+    term = __fmul_rn(proj, __fsub_rn(s_red[8], s_sh[t]));
+    a.grad[base + (int64_t)ab * N + t] = __fmul_rn(gscale, __fsub_rn(s_py[t], proj));
+  }
+  const float part = fast_sum(term);
+  if (!a.loss_out && !a.prio_out) return;
+  if (lane == 0) s_red[wave] = part;
+  __syncthreads();
+  if (t == 0) {
+    const float loss = __fadd_rn(__fadd_rn(__fadd_rn(s_red[0], s_red[1]), s_red[2]), s_red[3]);
+    if (a.loss_out) a.loss_out[b] = loss;
+    if (a.prio_out) a.prio_out[b] = sqrt_rn(__fadd_rn(loss, 1e-10f));
+  }
+}
+
 // mean(w * loss) for summaries (rb:298-301); launched only when requested.
 __global__ __launch_bounds__(64) void k_wmean(const float* loss, const float* probs, int B,
                                               float* out) {
@@ -596,6 +762,53 @@ __global__ __launch_bounds__(256) void k_dqn(const float* oq, const float* tq, c
     float mx = tq[(int64_t)b * A];
     for (int j = 1; j < A; ++j) mx = fmaxf(mx, tq[(int64_t)b * A + j]);
     // r + cumulative_gamma * max_a Q' * (1 - terminal)   (dqn:298-299)
+    const float target =
+        __fadd_rn(rew[b], __fmul_rn(__fmul_rn(cg, mx), __fsub_rn(1.0f, (float)term[b])));
+    const int ab = act[b];
+    const float err = __fsub_rn(oq[(int64_t)b * A + ab], target);  // predictions - labels
+    const float ae = fabsf(err);
+    const float quad = fminf(ae, 1.0f);
+    const float lin = __fsub_rn(ae, quad);
+    const float loss = __fadd_rn(__fmul_rn(__fmul_rn(0.5f, quad), quad), lin);
+    if (loss_out) loss_out[b] = loss;
+    part = __fadd_rn(part, loss);
+    const float g = __fmul_rn(fminf(fmaxf(err, -1.0f), 1.0f), invB);
+    for (int j = 0; j < A; ++j) grad[(int64_t)b * A + j] = (j == ab) ? g : 0.0f;
+  }
+  part = wave_sum(part);
+  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = part;
+  __syncthreads();
+  if (threadIdx.x == 0 && mean_out) {
+    float t = 0.0f;
+    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t = __fadd_rn(t, s_red[i]);
+    mean_out[0] = __fdiv_rn(t, (float)B);
+  }
+}
+
+// Double DQN: k_dqn with the greedy next action taken from `sq` (the online network on s':
+// first argmax in action order, strict >) and evaluated on tq (iqn:183-188's rule on
+// dqn:298-299).  Everything else is k_dqn's, operation for operation; with sq == tq the
+// evaluated value is the maximum itself, so every output is bitwise k_dqn's.
+__global__ __launch_bounds__(256) void k_dqn_double(const float* oq, const float* tq,
+                                                    const float* sq, const int32_t* act,
+                                                    const float* rew, const uint8_t* term, int B,
+                                                    int A, float cg, float* grad, float* loss_out,
+                                                    float* mean_out) {
+  __shared__ float s_red[4];
+  float part = 0.0f;
+  const float invB = __fdiv_rn(1.0f, (float)B);
+  for (int b = threadIdx.x; b < B; b += blockDim.x) {
+    int astar = 0;
+    float best = sq[(int64_t)b * A];
+    for (int j = 1; j < A; ++j) {
+      const float v = sq[(int64_t)b * A + j];
+      if (v > best) {
+        best = v;
+        astar = j;
+      }
+    }
+    const float mx = tq[(int64_t)b * A + astar];
+    // r + cumulative_gamma * Q'(s', argmax_a Q(s', a)) * (1 - terminal)
     const float target =
         __fadd_rn(rew[b], __fmul_rn(__fmul_rn(cg, mx), __fsub_rn(1.0f, (float)term[b])));
     const int ab = act[b];
@@ -916,6 +1129,36 @@ int dq_c51_loss(const float* online_logits, const float* target_logits, const in
   return DQ_OK;
 }
 
+int dq_c51_loss_double(const float* online_logits, const float* target_logits,
+                       const float* select_logits, const int32_t* actions, const float* rewards,
+                       const uint8_t* terminals, const float* probs, const float* support,
+                       int32_t batch, int32_t num_actions, int32_t num_atoms,
+                       float cumulative_gamma, float* grad_logits, float* loss_out,
+                       float* priorities_out, float* mean_loss_out, void* stream) {
+  DQ_CHECK_ARG(online_logits && target_logits && actions && rewards && terminals && support &&
+                   grad_logits,
+               "null argument");
+  DQ_CHECK_ARG(select_logits, "null select");
+  DQ_CHECK_ARG(num_atoms >= 2 && num_atoms <= kC51WideMaxAtoms, "num_atoms must be in [2, 256]");
+  DQ_CHECK_ARG(batch >= 1 && num_actions >= 1 && num_actions <= 256, "bad batch / num_actions");
+  DQ_CHECK_ARG(!mean_loss_out || loss_out, "mean_loss_out needs loss_out");
+  DQ_CHECK_ARG(num_actions <= 64, "num_actions must be <= 64");
+  C51Args a{online_logits, target_logits, actions, rewards, terminals, probs, support,
+            batch, num_actions, num_atoms, cumulative_gamma, grad_logits, loss_out,
+            priorities_out, mean_loss_out};
+  const size_t shm = (size_t)c51_double_floats(num_actions, num_atoms) * sizeof(float);
+  auto kern = probs ? k_c51_double<true> : k_c51_double<false>;
+  hipLaunchKernelGGL(kern, dim3(batch), dim3(kC51WideT), shm, (hipStream_t)stream, a,
+                     select_logits);
+  DQ_CHECK_LAUNCH("k_c51_double");
+  if (mean_loss_out) {
+    hipLaunchKernelGGL(k_wmean, dim3(1), dim3(64), 0, (hipStream_t)stream, loss_out, probs, batch,
+                       mean_loss_out);
+    DQ_CHECK_LAUNCH("k_wmean");
+  }
+  return DQ_OK;
+}
+
 int dq_c51_loss_fused(const float* online_parts, const float* online_bias,
                       const float* target_parts, const float* target_bias, int32_t n_parts,
                       const int32_t* actions, const float* rewards, const uint8_t* terminals,
@@ -997,6 +1240,21 @@ int dq_dqn_huber_loss(const float* online_q, const float* target_q, const int32_
                      actions, rewards, terminals, batch, num_actions, cumulative_gamma, grad_q,
                      loss_out, mean_loss_out);
   DQ_CHECK_LAUNCH("k_dqn");
+  return DQ_OK;
+}
+
+int dq_dqn_huber_loss_double(const float* online_q, const float* target_q, const float* select_q,
+                             const int32_t* actions, const float* rewards,
+                             const uint8_t* terminals, int32_t batch, int32_t num_actions,
+                             float cumulative_gamma, float* grad_q, float* loss_out,
+                             float* mean_loss_out, void* stream) {
+  DQ_CHECK_ARG(online_q && target_q && actions && rewards && terminals && grad_q, "null argument");
+  DQ_CHECK_ARG(select_q, "null select");
+  DQ_CHECK_ARG(batch >= 1 && num_actions >= 1, "bad sizes");
+  hipLaunchKernelGGL(k_dqn_double, dim3(1), dim3(256), 0, (hipStream_t)stream, online_q, target_q,
+                     select_q, actions, rewards, terminals, batch, num_actions, cumulative_gamma,
+                     grad_q, loss_out, mean_loss_out);
+  DQ_CHECK_LAUNCH("k_dqn_double");
   return DQ_OK;
 }
 

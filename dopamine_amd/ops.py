@@ -22,8 +22,10 @@ def _c(t, dtype):
 
 
 def c51_loss(online_logits, target_logits, actions, rewards, terminals, support, cumulative_gamma,
-             probs=None, out=None):
-  """rainbow_agent.py:200-305.  Returns dict(grad, loss, priorities, mean_loss)."""
+             probs=None, out=None, select_logits=None):
+  """rainbow_agent.py:200-305.  Returns dict(grad, loss, priorities, mean_loss).
+  select_logits (B, A, N): double-DQN targets -- the greedy next action from these logits'
+  Q-values (the online network on s'), evaluated on target_logits (dq_c51_loss_double)."""
   B, A, N = online_logits.shape
   f32 = torch.float32
   if out is None:
@@ -31,6 +33,14 @@ def c51_loss(online_logits, target_logits, actions, rewards, terminals, support,
     out = dict(grad=torch.empty_like(online_logits), loss=torch.empty(B, dtype=f32, device=dev),
                priorities=torch.empty(B, dtype=f32, device=dev),
                mean_loss=torch.empty(1, dtype=f32, device=dev))
+  if select_logits is not None:
+    assert select_logits.shape == target_logits.shape
+    _lib.call('dq_c51_loss_double', p(_c(online_logits, f32)), p(_c(target_logits, f32)),
+              p(_c(select_logits, f32)), p(_c(actions, torch.int32)), p(_c(rewards, f32)),
+              p(_c(terminals, torch.uint8)), p(probs if probs is None else _c(probs, f32)),
+              p(_c(support, f32)), B, A, N, float(cumulative_gamma), p(out['grad']),
+              p(out['loss']), p(out['priorities']), p(out['mean_loss']), _stream(online_logits))
+    return out
   _lib.call('dq_c51_loss', p(_c(online_logits, f32)), p(_c(target_logits, f32)),
             p(_c(actions, torch.int32)), p(_c(rewards, f32)), p(_c(terminals, torch.uint8)),
             p(probs if probs is None else _c(probs, f32)), p(_c(support, f32)), B, A, N,
@@ -90,14 +100,23 @@ def c51_loss_online(online, target_m, actions, probs=None, out=None, logits_out=
   return out
 
 
-def dqn_huber_loss(online_q, target_q, actions, rewards, terminals, cumulative_gamma, out=None):
-  """dqn_agent.py:283-322."""
+def dqn_huber_loss(online_q, target_q, actions, rewards, terminals, cumulative_gamma, out=None,
+                   select_q=None):
+  """dqn_agent.py:283-322.  select_q (B, A): double-DQN targets -- the greedy next action from
+  select_q (the online network on s'), evaluated on target_q (dq_dqn_huber_loss_double)."""
   B, A = online_q.shape
   f32 = torch.float32
   if out is None:
     dev = online_q.device
     out = dict(grad=torch.empty_like(online_q), loss=torch.empty(B, dtype=f32, device=dev),
                mean_loss=torch.empty(1, dtype=f32, device=dev))
+  if select_q is not None:
+    assert select_q.shape == target_q.shape
+    _lib.call('dq_dqn_huber_loss_double', p(_c(online_q, f32)), p(_c(target_q, f32)),
+              p(_c(select_q, f32)), p(_c(actions, torch.int32)), p(_c(rewards, f32)),
+              p(_c(terminals, torch.uint8)), B, A, float(cumulative_gamma), p(out['grad']),
+              p(out['loss']), p(out['mean_loss']), _stream(online_q))
+    return out
   _lib.call('dq_dqn_huber_loss', p(_c(online_q, f32)), p(_c(target_q, f32)),
             p(_c(actions, torch.int32)), p(_c(rewards, f32)), p(_c(terminals, torch.uint8)), B, A,
             float(cumulative_gamma), p(out['grad']), p(out['loss']), p(out['mean_loss']),

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define DQ_ABI_VERSION 11
+#define DQ_ABI_VERSION 12
 
 /* host-side return codes */
 #define DQ_OK 0
@@ -264,6 +264,21 @@ int dq_c51_loss(const float* online_logits, const float* target_logits, const in
                 float cumulative_gamma, float* grad_logits, float* loss_out,
                 float* priorities_out, float* mean_loss_out, void* stream);
 
+/* dq_c51_loss with double-DQN targets: the rule of implicit_quantile_agent.py:183-188
+ * (greedy next action from the online network on s', evaluated with the target network)
+ * generalised to C51.  select_logits (B, A, N): the online network's logits on next_state;
+ * a*_b = first argmax_a sum_i z_i softmax(select_logits[b, a])_i, the target distribution is
+ * softmax(target_logits[b, a*_b]); projection, cross-entropy, PER weights and priorities are
+ * dq_c51_loss's.  Same limits and status codes (2 <= num_atoms <= 256, num_actions <= 64; a
+ * NULL select_logits is DQ_E_ARG); one kernel for every num_atoms, fixed-order reductions.
+ * With select_logits == target_logits every output is bitwise dq_c51_loss's. */
+int dq_c51_loss_double(const float* online_logits, const float* target_logits,
+                       const float* select_logits, const int32_t* actions, const float* rewards,
+                       const uint8_t* terminals, const float* probs, const float* support,
+                       int32_t batch, int32_t num_actions, int32_t num_atoms,
+                       float cumulative_gamma, float* grad_logits, float* loss_out,
+                       float* priorities_out, float* mean_loss_out, void* stream);
+
 /* The online half of dq_c51_loss_fused (rainbow_agent.py:253-305: softmax cross-entropy of
    the chosen online logits against the projected target distribution, PER weights, new
    priorities, dlogits and d h) given target_m (B, num_atoms) from dq_cnn_forward_fused_c51;
@@ -299,6 +314,17 @@ int dq_dqn_huber_loss(const float* online_q, const float* target_q, const int32_
                       const float* rewards, const uint8_t* terminals, int32_t batch,
                       int32_t num_actions, float cumulative_gamma, float* grad_q,
                       float* loss_out, float* mean_loss_out, void* stream);
+/* dq_dqn_huber_loss with double-DQN targets: the rule of implicit_quantile_agent.py:183-188
+   generalised to DQN.  select_q (B, A): the online network's Q-values on next_state;
+   a*_b = first argmax_a select_q[b, a] and target_b = r_b + gamma^n target_q[b, a*_b]
+   (1 - terminal_b), the same three fp32 operations as dq_dqn_huber_loss.  Same checks and
+   status codes (a NULL select_q is DQ_E_ARG).  With select_q == target_q every output is
+   bitwise dq_dqn_huber_loss's. */
+int dq_dqn_huber_loss_double(const float* online_q, const float* target_q, const float* select_q,
+                             const int32_t* actions, const float* rewards,
+                             const uint8_t* terminals, int32_t batch, int32_t num_actions,
+                             float cumulative_gamma, float* grad_q, float* loss_out,
+                             float* mean_loss_out, void* stream);
 /* dq_dqn_huber_loss on the CNN's fc2 k-band partials (dq_cnn_forward_fused), the DQN fast
    path (dqn_agent.py:283-322): Q / Q' = the n_parts partial slabs [n_parts][B][A] summed in
    order + bias (bitwise dq_cnn_forward's outputs, written to *_q_out when non-NULL); target,

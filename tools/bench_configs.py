@@ -5,7 +5,10 @@ _train_step cadence), for DESIGN.md -- not the bench line:
   config 2: DQN / Pong   -- 6 actions, uniform replay, n = 1, TF1 centered RMSProp, B = 32
   config 5: IQN / Breakout -- 4 actions, n = 3, Adam, B = 64 (quantile-Huber kernel)
 
-    python tools/bench_configs.py [steps] [dqn_pong|iqn_breakout|all]
+    python tools/bench_configs.py [steps] [dqn_pong|iqn_breakout|all] [keyword=0|1 ...]
+
+``rainbow`` (only when named) is config 3, bench.py's agent, for keyword overrides such as
+``double_dqn=1`` or ``fused_head=0``.
 """
 import gc
 import json
@@ -57,6 +60,8 @@ def main():
   if which in ('all', 'iqn_breakout'):
     res['iqn_breakout'] = measure(lambda: bench.build_iqn_breakout(dev, **extra), 4,
                                   max(steps // 3, 50))
+  if which == 'rainbow':    # config 3, bench.py's own agent: for keyword overrides (double_dqn=1)
+    res['rainbow'] = measure(lambda: bench.build_agent(9, 1_000_000, 32, dev, **extra), 9, steps)
   print(json.dumps(res))
 
 

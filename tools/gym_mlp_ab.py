@@ -15,9 +15,11 @@ Prints every round, then per loop the medians, the spread (max - min) of each ar
 smallest HIP / PyTorch pair ratio and the A/A difference.
     python tools/gym_mlp_ab.py [--rounds 7] [--configs rainbow_cartpole dqn_cartpole]
 --configs also takes dqn_acrobot (the 24-24 MLP with plain gradient descent) and
-dqn_acrobot_fourier / dqn_cartpole_fourier (the Fourier-basis networks on fourier.hip).
---profile-arm runs 300 learner steps and 300 agent steps of the HIP arm only (the run to put
-under a kernel-trace profiler for the per-launch table)."""
+dqn_acrobot_fourier / dqn_cartpole_fourier (the Fourier-basis networks on fourier.hip),
+double_dqn_acrobot / double_rainbow_cartpole (the double-DQN configs: name the plain config
+too for the flag's cost in the same session) and c51_cartpole_201 / c51_cartpole_201+double.
+--profile-arm runs 300 learner steps and 300 agent steps of the HIP arm only, of every config
+named (the run to put under a kernel-trace profiler for the per-launch table)."""
 import argparse
 import os
 import random
@@ -41,13 +43,24 @@ CONFIGS = {'rainbow_cartpole': (os.path.join(_AGENTS, 'rainbow', 'configs', 'rai
 # (measured when named with --configs)
 for _n in ('dqn_acrobot', 'dqn_acrobot_fourier', 'dqn_cartpole_fourier'):
   CONFIGS[_n] = (os.path.join(_AGENTS, 'dqn', 'configs', _n + '.gin'), 'DQNAgent')
+# the double-DQN configs (run beside dqn_acrobot / rainbow_cartpole for the flag's cost)
+CONFIGS['double_dqn_acrobot'] = (os.path.join(_AGENTS, 'dqn', 'configs', 'double_dqn_acrobot.gin'),
+                                 'DQNAgent')
+CONFIGS['double_rainbow_cartpole'] = (
+    os.path.join(_AGENTS, 'rainbow', 'configs', 'double_rainbow_cartpole.gin'), 'RainbowAgent')
+# the 201-atom support (the chunked regime of the C51 loss), plain and with the flag bound (a
+# third element: extra bindings)
+_C201 = os.path.join(_AGENTS, 'rainbow', 'configs', 'c51_cartpole_201.gin')
+CONFIGS['c51_cartpole_201'] = (_C201, 'RainbowAgent')
+CONFIGS['c51_cartpole_201+double'] = (_C201, 'RainbowAgent', ['RainbowAgent.double_dqn = True'])
 DEFAULT_CONFIGS = ['rainbow_cartpole', 'dqn_cartpole']
 
 
 def build(config, hip):
-  gin, cls = CONFIGS[config]
+  gin, cls, *extra = CONFIGS[config]
   gin_lite.clear_config()
-  run_experiment.load_gin_configs([gin], ['%s.use_hip_mlp = %s' % (cls, bool(hip))])
+  run_experiment.load_gin_configs(
+      [gin], ['%s.use_hip_mlp = %s' % (cls, bool(hip))] + (extra[0] if extra else []))
   env = gym_lib.create_gym_environment()
   env.environment.seed(0)
   np.random.seed(0)
@@ -123,9 +136,10 @@ def main():
   args = ap.parse_args()
   torch.cuda.set_device(0)
   if args.profile_arm:
-    agent, env = build(args.configs[0], True)
-    print('profile arm: %.1f gradient steps/s, %.1f env steps/s' % (
-        run_learner(agent, 300), run_agent_loop(agent, env, 300)), flush=True)
+    for config in args.configs:           # (several: their kernels side by side in one trace)
+      agent, env = build(config, True)
+      print('profile arm %s: %.1f gradient steps/s, %.1f env steps/s' % (
+          config, run_learner(agent, 300), run_agent_loop(agent, env, 300)), flush=True)
     return
   for config in args.configs:
     arms = {'hip': build(config, True), 'torch': build(config, False), 'hip2': build(config, True)}
