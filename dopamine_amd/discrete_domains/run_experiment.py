@@ -31,6 +31,7 @@ from dopamine_amd.agents.dqn import dqn_agent
 from dopamine_amd.agents.implicit_quantile import implicit_quantile_agent
 from dopamine_amd.agents.optimizers import (AdamOptimizer, GradientDescentOptimizer,
                                             RMSPropOptimizer)
+from dopamine_amd.agents.quantile import quantile_agent
 from dopamine_amd.agents.rainbow import rainbow_agent
 from dopamine_amd.discrete_domains import gym_lib  # noqa: F401 -- registers gym refs/constants
 from dopamine_amd.utils import checkpointer
@@ -70,7 +71,8 @@ def load_gin_configs(gin_files, gin_bindings):
 _AGENTS = {'dqn': (dqn_agent, 'DQNAgent', 'WrappedReplayBuffer'),
            'rainbow': (rainbow_agent, 'RainbowAgent', 'WrappedPrioritizedReplayBuffer'),
            'implicit_quantile': (implicit_quantile_agent, 'ImplicitQuantileAgent',
-                                 'WrappedPrioritizedReplayBuffer')}
+                                 'WrappedPrioritizedReplayBuffer'),
+           'quantile': (quantile_agent, 'QuantileAgent', 'WrappedPrioritizedReplayBuffer')}
 
 
 def _agent_kwargs(agent_name):

@@ -167,6 +167,31 @@ def iqn_loss(online_qv, target_qv, target_qv_action, taus, actions, rewards, ter
   return out
 
 
+def qr_loss(online_q, target_q, actions, rewards, terminals, cumulative_gamma, kappa=1.0,
+            probs=None, out=None, select_q=None):
+  """QR-DQN's fixed-quantile regression loss (dq_qr_loss) on (B, A, N) quantile values, the
+  Rainbow head's layout.  select_q (B, A, N): double-DQN targets -- the greedy next action from
+  these rows' means (the online network on s'), evaluated on target_q; None: target_q itself.
+  Returns dict(grad, loss, priorities, mean_loss); ``out`` as ops.c51_loss's."""
+  B, A, N = online_q.shape
+  f32 = torch.float32
+  if out is None:
+    dev = online_q.device
+    out = dict(grad=torch.empty_like(online_q), loss=torch.empty(B, dtype=f32, device=dev),
+               priorities=torch.empty(B, dtype=f32, device=dev),
+               mean_loss=torch.empty(1, dtype=f32, device=dev))
+  assert target_q.shape == online_q.shape
+  if select_q is not None:
+    assert select_q.shape == target_q.shape
+    select_q = _c(select_q, f32)
+  _lib.call('dq_qr_loss', p(_c(online_q, f32)), p(_c(target_q, f32)), p(select_q),
+            p(_c(actions, torch.int32)), p(_c(rewards, f32)), p(_c(terminals, torch.uint8)),
+            p(probs if probs is None else _c(probs, f32)), B, A, N, float(cumulative_gamma),
+            float(kappa), p(out['grad']), p(out['loss']), p(out['priorities']),
+            p(out['mean_loss']), _stream(online_q))
+  return out
+
+
 class TF1Adam(object):
   """tf.train.AdamOptimizer over one flat fp32 buffer (ApplyAdam semantics)."""
 

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define DQ_ABI_VERSION 12
+#define DQ_ABI_VERSION 13
 
 /* host-side return codes */
 #define DQ_OK 0
@@ -348,6 +348,31 @@ int dq_iqn_loss(const float* online_qv, const float* target_qv, const float* tar
                 int32_t num_tau, int32_t num_tau_prime, int32_t num_quantile,
                 float cumulative_gamma, float kappa, float* grad_qv, float* loss_out,
                 float* mean_loss_out, void* stream);
+
+/* QR-DQN's fixed-quantile regression loss (Dabney et al., AAAI 2018, eq. 10; upstream
+ * Dopamine's QuantileAgent) with PER weights and new priorities (ABI 13).  online_q, target_q
+ * and select_q are (B, A, N) float32, quantile index last (the Rainbow head's layout);
+ * select_q may be NULL, meaning target_q (with double-DQN targets it is the online network's
+ * output on next_state).  With tau_i = (i + 0.5) / N:
+ *   a*_b   = first argmax_a (sum_i select_q[b, a, i]) / N
+ *   y_bj   = r_b + gamma^n (1 - terminal_b) target_q[b, a*_b, j]
+ *   u_bij  = y_bj - online_q[b, actions_b, i]
+ *   L_k(u) = u^2 / 2 if |u| <= kappa else kappa (|u| - kappa / 2)   (derivative 0 at u = 0)
+ *   loss_b = sum_i (1/N) sum_j |tau_i - 1{u_bij < 0}| L_k(u_bij) / kappa
+ * (the / kappa is dq_iqn_loss's form; at kappa = 1 it is the paper's).  priorities_out =
+ * sqrt(loss + 1e-10) of the unweighted loss and w_b = (p_b + 1e-10)^-1/2 / max_b'(..) are
+ * dq_c51_loss's rules; probs NULL => w_b = 1.  grad (B, A, N) is fully written:
+ * d mean_b(w_b loss_b) / d online_q, zeros off the taken action.  loss_out / priorities_out
+ * (B,), mean_loss_out (1,) = mean_b(w_b loss_b): may be NULL.
+ * Limits: 1 <= num_quantiles <= 256, 1 <= num_actions <= 64, kappa > 0, any batch.  Anything
+ * else -- also a NULL grad, or a mean_loss_out without a loss_out -- is DQ_E_ARG before a
+ * launch, with nothing written.  Fixed-order reductions, no atomics: two calls on the same
+ * inputs are bitwise equal, and select_q = NULL is bitwise select_q = target_q. */
+int dq_qr_loss(const float* online_q, const float* target_q, const float* select_q,
+               const int32_t* actions, const float* rewards, const uint8_t* terminals,
+               const float* probs, int32_t batch, int32_t num_actions, int32_t num_quantiles,
+               float cumulative_gamma, float kappa, float* grad, float* loss_out,
+               float* priorities_out, float* mean_loss_out, void* stream);
 
 /* tf.train.AdamOptimizer.apply_gradients over ONE flat fp32 parameter buffer.
  * state = {beta1_power, beta2_power}[2] (float32, device; slot 0 initialised to

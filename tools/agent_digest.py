@@ -83,11 +83,24 @@ def iqn(**kw):
   return a
 
 
+def quantile(**kw):
+  """A Nature-CNN QuantileAgent (101 quantiles) over tests/test_gpu_agent.py's buffer fill."""
+  from dopamine_amd.agents.quantile.quantile_agent import QuantileAgent
+  from tests.test_gpu_agent import _fill
+  seed()
+  a = QuantileAgent(num_actions=4, num_atoms=101, update_horizon=3, replay_capacity=3000,
+                    batch_size=32, min_replay_history=100, target_update_period=28, **kw)
+  _fill(a._replay.memory, 4, 3)
+  return a
+
+
 def gym(config):
-  """A classic-control agent from its gin file, filled by random-action episodes; it then acts
-  for 120 steps (per-call gradient steps with adds between them, one target sync)."""
+  """A classic-control agent from its gin file (a name of tests/test_gpu_gym_agents.py, or a
+  path below dopamine_amd/agents), filled by random-action episodes; it then acts for 120
+  steps (per-call gradient steps with adds between them, one target sync)."""
   from tests import test_gpu_gym_agents as G
-  env, agent = G._make(getattr(G, config), [])
+  path = getattr(G, config, None) or os.path.join(ROOT, 'dopamine_amd', 'agents', config)
+  env, agent = G._make(path, [])
   G._fill(env, agent, 1500)
   agent.begin_episode(env.reset())
   for _ in range(120):
@@ -142,6 +155,14 @@ CASES = {
     'c51_acrobot_mlp': lambda: digest(gym('C51_ACROBOT')),
     'rainbow_cartpole_mlp': lambda: digest(gym('RAINBOW_CARTPOLE')),
     'dqn_cartpole_torch': lambda: digest(gym('DQN_CARTPOLE')),
+    # QR-DQN (dq_qr_loss): the Nature-CNN schedules and the classic-control configs
+    'quantile_loop': lambda: digest(loop(quantile())),
+    'quantile_per_call': lambda: digest(per_call(quantile())),
+    'quantile_double_loop': lambda: digest(loop(quantile(double_dqn=True))),
+    'quantile_cartpole_mlp': lambda: digest(gym('quantile/configs/quantile_cartpole.gin')),
+    'double_quantile_cartpole_mlp': lambda: digest(
+        gym('quantile/configs/double_quantile_cartpole.gin')),
+    'quantile_acrobot_mlp': lambda: digest(gym('quantile/configs/quantile_acrobot.gin')),
 }
 for _zero in (False, True):
   for _native in (True, False):

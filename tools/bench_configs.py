@@ -8,7 +8,10 @@ _train_step cadence), for DESIGN.md -- not the bench line:
     python tools/bench_configs.py [steps] [dqn_pong|iqn_breakout|all] [keyword=0|1 ...]
 
 ``rainbow`` (only when named) is config 3, bench.py's agent, for keyword overrides such as
-``double_dqn=1`` or ``fused_head=0``.
+``double_dqn=1`` or ``fused_head=0``.  ``quantile`` (only when named) is QR-DQN on the same
+buffer, batch and optimizer schedule: QuantileAgent with 9 actions and 200 quantiles as upstream's
+quantile.gin binds it (n = 3, PER, Adam 5e-5 / 3.125e-4), for the loss kernel's cost beside
+``rainbow fused_head=0``, the schedule it shares.
 """
 import gc
 import json
@@ -46,6 +49,18 @@ def measure(make, actions, steps, warmup=20):
   return out
 
 
+def build_quantile(device, **kw):
+  from dopamine_amd.agents.optimizers import AdamOptimizer
+  from dopamine_amd.agents.quantile.quantile_agent import QuantileAgent
+  agent = QuantileAgent(num_actions=9, num_atoms=200, kappa=1.0, update_horizon=3, gamma=0.99,
+                        replay_scheme='prioritized', min_replay_history=20000, update_period=4,
+                        target_update_period=8000,
+                        optimizer=AdamOptimizer(learning_rate=0.00005, epsilon=0.0003125),
+                        replay_capacity=1_000_000, batch_size=32, device=device, seed=0, **kw)
+  agent.keep_gradients = False      # as bench.build_agent
+  return agent
+
+
 def main():
   steps = int(sys.argv[1]) if len(sys.argv) > 1 else 300
   which = sys.argv[2] if len(sys.argv) > 2 else 'all'
@@ -62,6 +77,8 @@ def main():
                                   max(steps // 3, 50))
   if which == 'rainbow':    # config 3, bench.py's own agent: for keyword overrides (double_dqn=1)
     res['rainbow'] = measure(lambda: bench.build_agent(9, 1_000_000, 32, dev, **extra), 9, steps)
+  if which == 'quantile':
+    res['quantile'] = measure(lambda: build_quantile(dev, **extra), 9, steps)
   print(json.dumps(res))
 
 

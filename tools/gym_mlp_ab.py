@@ -17,7 +17,8 @@ smallest HIP / PyTorch pair ratio and the A/A difference.
 --configs also takes dqn_acrobot (the 24-24 MLP with plain gradient descent) and
 dqn_acrobot_fourier / dqn_cartpole_fourier (the Fourier-basis networks on fourier.hip),
 double_dqn_acrobot / double_rainbow_cartpole (the double-DQN configs: name the plain config
-too for the flag's cost in the same session) and c51_cartpole_201 / c51_cartpole_201+double.
+too for the flag's cost in the same session), c51_cartpole_201 / c51_cartpole_201+double and
+quantile_cartpole / double_quantile_cartpole / quantile_acrobot (QR-DQN, 200 quantiles).
 --profile-arm runs 300 learner steps and 300 agent steps of the HIP arm only, of every config
 named (the run to put under a kernel-trace profiler for the per-launch table)."""
 import argparse
@@ -53,6 +54,12 @@ CONFIGS['double_rainbow_cartpole'] = (
 _C201 = os.path.join(_AGENTS, 'rainbow', 'configs', 'c51_cartpole_201.gin')
 CONFIGS['c51_cartpole_201'] = (_C201, 'RainbowAgent')
 CONFIGS['c51_cartpole_201+double'] = (_C201, 'RainbowAgent', ['RainbowAgent.double_dqn = True'])
+# QR-DQN on dq_qr_loss (200 quantiles: MLP outputs of 400 and 600)
+for _n in ('quantile_cartpole', 'double_quantile_cartpole', 'quantile_acrobot'):
+  CONFIGS[_n] = (os.path.join(_AGENTS, 'quantile', 'configs', _n + '.gin'), 'QuantileAgent')
+# (uniform weights: the loss kernel's instantiation without probabilities, for --profile-arm)
+CONFIGS['quantile_cartpole+uniform'] = CONFIGS['quantile_cartpole'] + (
+    ["QuantileAgent.replay_scheme = 'uniform'"],)
 DEFAULT_CONFIGS = ['rainbow_cartpole', 'dqn_cartpole']
 
 
