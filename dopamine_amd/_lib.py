@@ -9,7 +9,7 @@ import os
 from dopamine_amd import _build
 from dopamine_amd._build import HEADER, LIB_PATH  # noqa: F401
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 OK = 0
 (ST_OK, ST_EMPTY_TREE, ST_MAX_ATTEMPTS, ST_TAPE_EXHAUSTED, ST_NEG_PRIORITY, ST_TOO_FEW, ST_BAD_INDEX,
  ST_BROADCAST) = range(8)
@@ -203,6 +203,8 @@ SIGNATURES = {
     'dq_dqn_huber_loss_double': [_P, _P, _P, _P, _P, _P, _I32, _I32, _F, _P, _P, _P, _P],
     'dq_iqn_loss': [_P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _F, _F, _P, _P, _P, _P],
     'dq_qr_loss': [_P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _F, _F, _P, _P, _P, _P, _P],
+    'dq_dueling_forward': [_P, _I32, _I32, _I32, _P, _P],
+    'dq_dueling_backward': [_P, _I32, _I32, _I32, _P, _P],
     'dq_adam_tf1': [_P, _P, _P, _P, _P, _I32, _I64, _F, _F, _F, _F, _P],
     'dq_adam_tf1_part': [_P, _P, _P, _P, _P, _I32, _I64, _F, _F, _F, _F, _I32, _P],
     'dq_adam_tf1_multi': [ctypes.POINTER(TensorList), _P, _I32, _F, _F, _F, _F, _P],

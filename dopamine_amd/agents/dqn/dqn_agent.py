@@ -97,7 +97,8 @@ class DQNAgent(object):
                shard_optimizer=False,
                native_comm=True,
                exchange='collective',
-               double_dqn=False):
+               double_dqn=False,
+               dueling=False):
     assert num_actions is not None
     assert isinstance(observation_shape, tuple)      # abstract_agent.py:34
     self.num_actions = num_actions
@@ -151,6 +152,20 @@ class DQNAgent(object):
       # the second online forward would read there is not designed
       raise ValueError('double_dqn is not supported with data-parallel learners '
                        '(process_group)')
+    # Dueling heads (Wang et al. 2016; upstream's FullRainbowNetwork): the network's last layer
+    # has (A + 1) * N rows, the advantage stream then the value stream, and its output is
+    # (adv - mean_a adv) + val.  The executors apply the combine and its transpose
+    # (dq_dueling_forward / _backward), so the loss entries, the Q reduction, the acting path
+    # and every step schedule see the (B, A[, N]) output they always saw.
+    self.dueling = bool(dueling)
+    if self.dueling and process_group is not None:
+      # the exchanges' schedules are written for the fused loss kernels, which read fc2
+      # partials of an A * N head
+      raise ValueError('dueling is not supported with data-parallel learners (process_group)')
+    if self.dueling and isinstance(network, type) and issubclass(network,
+                                                                 networks.FourierDQNNetwork):
+      raise ValueError('dueling needs a network with a dense last layer; the Fourier-basis '
+                       'networks take no dueling head')
     self._online_next = None       # double_dqn: the online network's forward-only executor on s'
     self._peer = None
     self._dp = None                # N > 1: the collective exchange (data_parallel.Exchange)
@@ -319,6 +334,10 @@ class DQNAgent(object):
       d['target_out'] = self._ptgt[c]['q']
     if self._double():               # the online network's output on next_state (select)
       d['online_next_out'] = self._last_online_next.reshape(self._batch_size, -1)
+    if self.dueling:                 # the online network's raw head (the outputs above: combined)
+      exe = self._hip or self._mlp
+      d['online_head_out'] = (exe['online'].acts['head'] if exe is not None
+                              else self._last_online_head)
     return d
 
   def _trace_step(self, slot, c):
@@ -339,9 +358,16 @@ class DQNAgent(object):
         batch_size=self._batch_size, device=self._device)
 
   def _make_network(self, seed):
+    kw = self._network_kwargs()
     if self._is_gym_network():
-      return self.network(self.num_actions, device=self._device, seed=seed)
-    return self.network(self.num_actions, stack_size=self.stack_size, device=self._device, seed=seed)
+      return self.network(self.num_actions, device=self._device, seed=seed, **kw)
+    return self.network(self.num_actions, stack_size=self.stack_size, device=self._device,
+                        seed=seed, **kw)
+
+  def _network_kwargs(self):
+    """Constructor arguments only some networks take (a custom network without a ``dueling``
+    argument is constructed as before)."""
+    return {'dueling': True} if self.dueling else {}
 
   def _is_gym_network(self):
     return (isinstance(self.network, type) and
@@ -423,6 +449,10 @@ class DQNAgent(object):
       return self._hip['online'].forward(x)
     if self._mlp is not None:
       return self._mlp['online'].forward(x)
+    if self.dueling:                    # the PyTorch path: the raw head kept for the trace
+      head = self.online_convnet.head(self._state_input(x))
+      self._last_online_head = head.detach()
+      return self.online_convnet._combine(head)
     return self.online_convnet(self._state_input(x))
 
   def _target_net(self, x, slot):
@@ -554,8 +584,10 @@ class DQNAgent(object):
     backward each lose a launch (the Nature-CNN agents: DQN's Huber here, Rainbow's C51
     in its subclass).  Not with double_dqn: the fused loss kernels have no input for the
     online network's output on s', so that agent takes fused_head=False's schedule (stored
-    outputs, then the plain loss entry)."""
-    return self.fused_head and self._rides() and not self._double()
+    outputs, then the plain loss entry).  Nor with dueling: the fused loss kernels sum fc2
+    partials of an A * N head, and the combine needs the stored (A + 1) * N outputs, so that
+    agent takes the same stored-outputs schedule."""
+    return self.fused_head and self._rides() and not self._double() and not self.dueling
 
   def _fused_loss(self, t, c):
     """_online_loss on the CNN's fc2 partials: Q / Q' summed in the loss kernel

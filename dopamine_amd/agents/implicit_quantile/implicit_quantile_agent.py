@@ -35,7 +35,12 @@ class ImplicitQuantileAgent(rainbow_agent.RainbowAgent):
                double_dqn=False,
                summary_writer=None,
                summary_writing_frequency=500,
+               dueling=False,
                **kwargs):
+    if dueling:
+      # the IQN head's output is (N * B, A), one row per sampled quantile, and upstream's
+      # implicit-quantile network has no dueling form
+      raise ValueError('ImplicitQuantileAgent has no dueling head (dueling=True)')
     self.kappa = kappa
     self.num_tau_samples = num_tau_samples
     self.num_tau_prime_samples = num_tau_prime_samples

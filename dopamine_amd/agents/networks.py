@@ -93,6 +93,21 @@ def _xavier_uniform(shape, fan_in, fan_out, gen):
   return (torch.rand(shape, generator=gen) * 2 - 1) * limit
 
 
+def dueling_combine(head, num_actions, num_atoms=None):
+  """The dueling head (Wang et al. 2016, eq. 9) as a torch expression, so autograd
+  differentiates it.  head (B, (A + 1) * N): columns [0, A * N) the advantage stream
+  adv[b, a, z] (z fastest), columns [A * N, (A + 1) * N) the value stream val[b, z];
+  num_atoms None: N = 1 and a (B, A) result, else (B, A, N).
+  out[b, a, z] = (adv[b, a, z] - sum_a adv[b, a, z] / A) + val[b, z]: what dq_dueling_forward
+  computes on the HIP executors."""
+  A, N = int(num_actions), int(num_atoms or 1)
+  B = head.shape[0]
+  adv = head[:, :A * N].reshape(B, A, N)
+  val = head[:, A * N:].reshape(B, 1, N)
+  out = (adv - adv.sum(1, keepdim=True) / A) + val
+  return out.reshape(B, A) if num_atoms is None else out
+
+
 TORSO = [('conv1', (32, None, 8, 8), 4), ('conv2', (64, 32, 4, 4), 2), ('conv3', (64, 64, 3, 3), 1)]
 
 
@@ -100,6 +115,7 @@ class _Net(object):
   """Base: owns FlatParams; subclasses define shapes() and forward()."""
 
   tail_align = None
+  dueling = False
 
   def __init__(self, device, seed, init='rainbow'):
     self.fp = FlatParams(self.shapes(), device, self.tail_align)
@@ -112,11 +128,39 @@ class _Net(object):
           fan_in, fan_out = shape[1] * shape[2] * shape[3], shape[0] * shape[2] * shape[3]
         else:
           fan_in, fan_out = shape[1], shape[0]
-        if init == 'rainbow':
-          w = _variance_scaling_uniform(shape, fan_in, 1.0 / np.sqrt(3.0), gen)
+
+        def draw(shape, fan_out):
+          if init == 'rainbow':
+            return _variance_scaling_uniform(shape, fan_in, 1.0 / np.sqrt(3.0), gen)
+          return _xavier_uniform(shape, fan_in, fan_out, gen)
+
+        if self.dueling and name == self.HEAD + '_w':
+          # two dense layers in one matrix (upstream's FullRainbowNetwork): the advantage
+          # block, then the value block, each drawn with its own fan_out
+          rows = self.head_rows()
+          assert sum(rows) == shape[0]
+          w = torch.cat([draw((r,) + tuple(shape[1:]), r) for r in rows])
         else:
-          w = _xavier_uniform(shape, fan_in, fan_out, gen)
+          w = draw(shape, fan_out)
         self.fp[name].copy_(w.to(device))
+
+  HEAD = 'fc2'        # the last layer's parameter names: HEAD + '_w' / '_b'
+
+  def head_rows(self):
+    """dueling: the last layer's rows as (advantage block, value block)."""
+    n = getattr(self, 'N', None) or 1
+    return (self.A * n, n)
+
+  def _combine(self, head):
+    """The network's output from its last layer's: with ``dueling`` the combined
+    (B, A[, N]) head (dueling_combine), else the layer's output itself."""
+    n = getattr(self, 'N', None)
+    if self.dueling:
+      return dueling_combine(head, self.A, n)
+    return head if n is None else head.view(-1, self.A, n)
+
+  def forward(self, x):
+    return self._combine(self.head(x))
 
   def parameters(self):
     return list(self.fp.params.values())
@@ -153,15 +197,21 @@ class NatureDQNNetwork(_Net):
   """atari_lib.py:85-105 -> q_values (B, A)."""
   tail_align = FC_BUCKET_ALIGN
 
-  def __init__(self, num_actions, stack_size=4, device='cuda', seed=0):
-    self.A, self.S = num_actions, stack_size
+  def __init__(self, num_actions, stack_size=4, device='cuda', seed=0, dueling=False):
+    self.A, self.S, self.dueling = num_actions, stack_size, bool(dueling)
     super().__init__(device, seed, init='xavier')
+
+  @property
+  def n_out(self):
+    """fc2's rows: A, or with ``dueling`` A + 1 (the value stream last)."""
+    return self.A + int(self.dueling)
 
   def shapes(self):
     return _torso_shapes(self.S) + [('fc1_w', (512, 7744)), ('fc1_b', (512,)),
-                                    ('fc2_w', (self.A, 512)), ('fc2_b', (self.A,))]
+                                    ('fc2_w', (self.n_out, 512)), ('fc2_b', (self.n_out,))]
 
-  def forward(self, x):
+  def head(self, x):
+    """fc2's raw output (B, n_out)."""
     h = F.relu(F.linear(_torso(self.fp, x), self.fp['fc1_w'], self.fp['fc1_b']))
     return F.linear(h, self.fp['fc2_w'], self.fp['fc2_b'])
 
@@ -170,17 +220,24 @@ class RainbowNetwork(_Net):
   """atari_lib.py:108-144 -> logits (B, A, N); q/probabilities derived."""
   tail_align = FC_BUCKET_ALIGN
 
-  def __init__(self, num_actions, num_atoms=51, stack_size=4, device='cuda', seed=0):
-    self.A, self.N, self.S = num_actions, num_atoms, stack_size
+  def __init__(self, num_actions, num_atoms=51, stack_size=4, device='cuda', seed=0,
+               dueling=False):
+    self.A, self.N, self.S, self.dueling = num_actions, num_atoms, stack_size, bool(dueling)
     super().__init__(device, seed, init='rainbow')
+
+  @property
+  def n_out(self):
+    """fc2's rows: A * N, or with ``dueling`` (A + 1) * N (the value stream last)."""
+    return (self.A + int(self.dueling)) * self.N
 
   def shapes(self):
     return _torso_shapes(self.S) + [('fc1_w', (512, 7744)), ('fc1_b', (512,)),
-                                    ('fc2_w', (self.A * self.N, 512)), ('fc2_b', (self.A * self.N,))]
+                                    ('fc2_w', (self.n_out, 512)), ('fc2_b', (self.n_out,))]
 
-  def forward(self, x):
+  def head(self, x):
+    """fc2's raw output (B, n_out)."""
     h = F.relu(F.linear(_torso(self.fp, x), self.fp['fc1_w'], self.fp['fc1_b']))
-    return F.linear(h, self.fp['fc2_w'], self.fp['fc2_b']).view(-1, self.A, self.N)
+    return F.linear(h, self.fp['fc2_w'], self.fp['fc2_b'])
 
 
 class ImplicitQuantileNetwork(_Net):
@@ -218,9 +275,11 @@ class BasicDiscreteDomainNetwork(_Net):
 
   MIN = MAX = None      # the domain's observation bounds (float64), set by subclasses
   GIN_NAME = None       # the reference's configurable, whose network_size binding is honoured
+  HEAD = 'out'
 
   def __init__(self, num_actions, num_atoms=None, stack_size=1, device='cuda', seed=0,
-               network_size=None):
+               network_size=None, dueling=False):
+    self.dueling = bool(dueling)
     if network_size is None:    # the gin binding (acrobot_dqn_network.network_size), or 512-512
       bound = gin_lite.query(self.GIN_NAME) if self.GIN_NAME else {}
       network_size = bound.get('network_size', (512, 512))
@@ -233,7 +292,8 @@ class BasicDiscreteDomainNetwork(_Net):
 
   @property
   def n_out(self):
-    return self.A * (self.N or 1)
+    """The last layer's rows: A * N, or with ``dueling`` (A + 1) * N (the value stream last)."""
+    return (self.A + int(self.dueling)) * (self.N or 1)
 
   def shapes(self):
     dims = [self.D] + list(self.sizes)
@@ -242,13 +302,13 @@ class BasicDiscreteDomainNetwork(_Net):
       s += [('fc%d_w' % i, (dims[i + 1], dims[i])), ('fc%d_b' % i, (dims[i + 1],))]
     return s + [('out_w', (self.n_out, dims[-1])), ('out_b', (self.n_out,))]
 
-  def forward(self, x):
+  def head(self, x):
+    """The last layer's raw output (B, n_out)."""
     h = x.reshape(x.shape[0], -1).float()
     h = 2.0 * ((h - self._min) / self._rng) - 1.0
     for i in range(len(self.sizes)):
       h = F.relu(F.linear(h, self.fp['fc%d_w' % i], self.fp['fc%d_b' % i]))
-    out = F.linear(h, self.fp['out_w'], self.fp['out_b'])
-    return out if self.N is None else out.view(-1, self.A, self.N)
+    return F.linear(h, self.fp['out_w'], self.fp['out_b'])
 
 
 _CARTPOLE_MIN = np.array([-2.4, -5., -math.pi / 12., -math.pi * 2.])
@@ -264,9 +324,9 @@ class CartpoleDQNNetwork(BasicDiscreteDomainNetwork):
   GIN_NAME = 'cartpole_dqn_network'
 
   def __init__(self, num_actions, device='cuda', seed=0, network_size=None, num_atoms=None,
-               stack_size=1):
+               stack_size=1, dueling=False):
     assert num_atoms is None
-    super().__init__(num_actions, None, stack_size, device, seed, network_size)
+    super().__init__(num_actions, None, stack_size, device, seed, network_size, dueling)
 
 
 class CartpoleRainbowNetwork(BasicDiscreteDomainNetwork):
@@ -276,8 +336,8 @@ class CartpoleRainbowNetwork(BasicDiscreteDomainNetwork):
   GIN_NAME = 'cartpole_rainbow_network'
 
   def __init__(self, num_actions, num_atoms=51, stack_size=1, device='cuda', seed=0,
-               network_size=None):
-    super().__init__(num_actions, num_atoms, stack_size, device, seed, network_size)
+               network_size=None, dueling=False):
+    super().__init__(num_actions, num_atoms, stack_size, device, seed, network_size, dueling)
 
 
 class AcrobotDQNNetwork(BasicDiscreteDomainNetwork):
@@ -287,9 +347,9 @@ class AcrobotDQNNetwork(BasicDiscreteDomainNetwork):
   GIN_NAME = 'acrobot_dqn_network'
 
   def __init__(self, num_actions, device='cuda', seed=0, network_size=None, num_atoms=None,
-               stack_size=1):
+               stack_size=1, dueling=False):
     assert num_atoms is None
-    super().__init__(num_actions, None, stack_size, device, seed, network_size)
+    super().__init__(num_actions, None, stack_size, device, seed, network_size, dueling)
 
 
 class AcrobotRainbowNetwork(BasicDiscreteDomainNetwork):
@@ -299,8 +359,8 @@ class AcrobotRainbowNetwork(BasicDiscreteDomainNetwork):
   GIN_NAME = 'acrobot_rainbow_network'
 
   def __init__(self, num_actions, num_atoms=51, stack_size=1, device='cuda', seed=0,
-               network_size=None):
-    super().__init__(num_actions, num_atoms, stack_size, device, seed, network_size)
+               network_size=None, dueling=False):
+    super().__init__(num_actions, num_atoms, stack_size, device, seed, network_size, dueling)
 
 
 def fourier_multipliers(in_dim, order):

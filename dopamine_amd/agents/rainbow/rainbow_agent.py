@@ -120,7 +120,7 @@ class RainbowAgent(dqn_agent.DQNAgent):
 
   def _make_network(self, seed):
     return self.network(self.num_actions, num_atoms=self._num_atoms, stack_size=self.stack_size,
-                        device=self._device, seed=seed)
+                        device=self._device, seed=seed, **self._network_kwargs())
 
   def _build_train_op(self):
     B, A, N, dev = self._batch_size, self.num_actions, self._num_atoms, self._device

@@ -11,6 +11,7 @@ import ctypes
 import torch
 
 from dopamine_amd import _lib
+from dopamine_amd import ops
 
 
 CnnParams, CnnActs = _lib.CnnParams, _lib.CnnActs
@@ -31,7 +32,12 @@ def _params_struct(fp, buf, n_out, in_ch):
 class HipNatureCNN(object):
   """Executes a ``NatureDQNNetwork`` / ``RainbowNetwork``'s parameters with the
   HIP kernels.  ``forward`` keeps its activations for ``backward``; use one
-  executor per concurrent stream (online vs target)."""
+  executor per concurrent stream (online vs target).  A dueling network's head is applied
+  here: fc2's (B, n_out = (A + 1) * N) output goes to ``acts['head']`` and wherever outputs
+  materialise (forward, forward_pair, forward_with_tail) dq_dueling_forward combines it into
+  ``acts['out']`` (B, A * N); every backward entry point takes the gradient of that and turns
+  it into fc2's with dq_dueling_backward (_backward_args).  The fused paths, which never
+  store fc2's output, refuse such a network."""
 
   def __init__(self, net, batch_size):
     fp = net.fp
@@ -46,6 +52,13 @@ class HipNatureCNN(object):
     mk = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
     self.acts = dict(a1=mk(B, 21, 21, 32), a2=mk(B, 11, 11, 64), a3=mk(B, 7744), h=mk(B, 512),
                      out=mk(B, self.n_out))
+    self.dueling = bool(getattr(net, 'dueling', False))
+    if self.dueling:
+      self.A, self.N = int(net.A), int(getattr(net, 'N', None) or 1)
+      assert self.n_out == (self.A + 1) * self.N
+      head = self.acts['out']                       # fc2's raw output
+      self.acts['out'] = mk(B, self.A * self.N)     # the combined head
+      self.dhead = mk(B, self.n_out)
     self.dacts = dict(a1=mk(B, 21, 21, 32), a2=mk(B, 11, 11, 64), a3=mk(B, 7744), h=mk(B, 512),
                       out=mk(1))
     nws = int(_lib.lib.dq_cnn_workspace_floats(B, self.n_out)) + 64
@@ -56,6 +69,9 @@ class HipNatureCNN(object):
     self._p = _params_struct(fp, fp.flat, self.n_out, self.in_ch)
     self._g = _params_struct(fp, fp.grad, self.n_out, self.in_ch)
     self._a = CnnActs(**{k: v.data_ptr() for k, v in self.acts.items()})
+    if self.dueling:
+      self.acts['head'] = head
+      self._a.out = head.data_ptr()
     self._d = CnnActs(**{k: v.data_ptr() for k, v in self.dacts.items()})
     self._x = None
 
@@ -77,7 +93,18 @@ class HipNatureCNN(object):
     _lib.check(_lib.lib.dq_cnn_forward(ctypes.byref(self._p), self.B, x.data_ptr(),
                                        ctypes.byref(self._a), self.ws.data_ptr(), self._stream(x)),
                'dq_cnn_forward')
+    return self._combined()
+
+  def _combined(self):
+    """The output buffer once fc2's has landed: a dueling network's combine runs here."""
+    if self.dueling:
+      ops.dueling_forward(self.acts['head'], self.A, self.N, out=self.acts['out'])
     return self.acts['out']
+
+  def _no_dueling(self, what):
+    if self.dueling:
+      raise ValueError('%s: no fused path for a dueling head (the fc2 partials are those of '
+                       '(A + 1) * N rows and the fused loss kernels read them as A * N)' % what)
 
   def forward_head(self, x):
     """The head of forward(x): conv1..conv3 and fc1's split-K partial sums (into
@@ -131,7 +158,13 @@ class HipNatureCNN(object):
 
   def _backward_args(self, dout):
     """dout as (B, n_out), and the arguments every backward entry point starts with:
-    parameters, gradients, batch, input, activations, dout, activation gradients, workspace."""
+    parameters, gradients, batch, input, activations, dout, activation gradients, workspace.
+    A dueling network's dout is the combined head's, (B, A * N): its one dq_dueling_backward
+    launch per step turns it into fc2's here."""
+    if self.dueling:
+      dout = dout.reshape(self.B, self.A * self.N)
+      assert dout.is_contiguous() and dout.dtype == torch.float32
+      dout = ops.dueling_backward(dout, self.A, self.N, out=self.dhead)
     dout = dout.reshape(self.B, self.n_out)
     assert dout.is_contiguous() and self._x is not None
     return dout, (ctypes.byref(self._p), ctypes.byref(self._g), self.B, self._x.data_ptr(),
@@ -236,7 +269,7 @@ def forward_pair(a, xa, b, xb):
       ctypes.byref(a._p), xa.data_ptr(), ctypes.byref(a._a), a.ws.data_ptr(),
       ctypes.byref(b._p), xb.data_ptr(), ctypes.byref(b._a), b.ws.data_ptr(), a.B,
       a._stream(xa)), 'dq_cnn_forward_pair')
-  return a.acts['out'], b.acts['out']
+  return a._combined(), b._combined()
 
 
 def forward_with_tail(a, xa, b):
@@ -249,11 +282,12 @@ def forward_with_tail(a, xa, b):
       ctypes.byref(a._p), xa.data_ptr(), ctypes.byref(a._a), a.ws.data_ptr(),
       ctypes.byref(b._p), ctypes.byref(b._a), b.ws.data_ptr(), a.B, a._stream(xa)),
       'dq_cnn_forward_with_tail')
-  return a.acts['out'], b.acts['out']
+  return a._combined(), b._combined()
 
 
 def fc2_parts(net):
   """The (16, B, n_out) view of ``net``'s fc2 k-band partials (forward_fused)."""
+  net._no_dueling('fc2_parts')
   off = int(_lib.lib.dq_cnn_fc2_parts_offset(net.B))
   n = 16 * net.B * net.n_out
   return net.ws[off:off + n].view(16, net.B, net.n_out)
@@ -275,6 +309,8 @@ def forward_fused(a, xa, b, fc1_b=True, conv3_b=False, part=None, conv2_b=False,
   ``backward_peer(..., defer_ag=True)``) into ``a``'s flat parameters ``var`` rides in the
   three conv launches (dq_cnn_forward_fused_peer).  Returns the two partial views."""
   assert a.B == b.B and a is not b
+  a._no_dueling('forward_fused')
+  b._no_dueling('forward_fused')
   xa = a._nhwc(xa)
   a._x = xa
   if peer is not None:
@@ -303,6 +339,8 @@ def forward_fused_c51(a, xa, b, rewards, terminals, support, cumulative_gamma, m
   / conv3 / fc1 -- and the target half of the C51 loss beside ``a``'s fused head, writing
   the projected target distribution into ``m_out`` (B, N).  part: as forward_fused."""
   assert a.B == b.B and a is not b
+  a._no_dueling('forward_fused_c51')
+  b._no_dueling('forward_fused_c51')
   xa = a._nhwc(xa)
   a._x = xa
   t = _lib.C51Target(rewards=rewards.data_ptr(), terminals=terminals.data_ptr(),

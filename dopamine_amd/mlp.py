@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from dopamine_amd import _lib
+from dopamine_amd import ops
 
 
 def _params_struct(net, buf):
@@ -38,7 +39,10 @@ def _params_struct(net, buf):
 class HipMLP(object):
   """Executes a ``BasicDiscreteDomainNetwork``'s parameters (read in place) with the HIP
   kernels.  ``forward`` keeps its activations for ``backward``; use one executor per
-  concurrent stream (online vs target)."""
+  concurrent stream (online vs target).  A dueling network's head is applied here: the last
+  layer's (B, n_out = (A + 1) * N) output goes to ``acts['head']``, dq_dueling_forward combines
+  it into ``acts['out']`` (B, A * N), which ``forward`` returns and ``backward`` takes the
+  gradient of (dq_dueling_backward into ``dhead``, then the MLP's backward on that)."""
 
   def __init__(self, net, batch_size):
     L = len(net.sizes)
@@ -52,7 +56,13 @@ class HipMLP(object):
     self.D, self.n_out = int(net.D), int(net.n_out)
     dev = net.fp.flat.device
     mk = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
+    self.dueling = bool(getattr(net, 'dueling', False))
     self.acts = dict(x0=mk(B, self.D), out=mk(B, self.n_out))
+    if self.dueling:
+      self.A, self.N = int(net.A), int(net.N or 1)
+      self.acts['head'] = self.acts['out']          # the last layer's raw output
+      self.acts['out'] = mk(B, self.A * self.N)     # the combined head
+      self.dhead = mk(B, self.n_out)
     self.dacts = {}
     for i, w in enumerate(net.sizes):
       self.acts['h%d' % i] = mk(B, w)
@@ -65,8 +75,9 @@ class HipMLP(object):
 
   @staticmethod
   def _acts_struct(t):
+    out = t.get('head', t.get('out'))     # the last layer writes the raw head
     s = _lib.MlpActs(x0=t['x0'].data_ptr() if 'x0' in t else None,
-                     out=t['out'].data_ptr() if 'out' in t else None)
+                     out=None if out is None else out.data_ptr())
     for i in range(4):
       if 'h%d' % i in t:
         s.h[i] = t['h%d' % i].data_ptr()
@@ -74,21 +85,25 @@ class HipMLP(object):
 
   def forward(self, x):
     """x: the states, B * D contiguous float64 or float32 values (any shape, e.g. the
-    gather's (B, 1, D, 1)).  Returns the (B, n_out) output buffer (overwritten by the next
-    call)."""
+    gather's (B, 1, D, 1)).  Returns the (B, n_out) output buffer, with a dueling network the
+    combined (B, A * N) one (overwritten by the next call)."""
     assert x.numel() == self.B * self.D and x.is_contiguous(), (tuple(x.shape), self.B, self.D)
     assert x.dtype in (torch.float64, torch.float32), x.dtype
     _lib.check(_lib.lib.dq_mlp_forward(ctypes.byref(self._p), self.B, x.data_ptr(),
                                        int(x.dtype == torch.float64), ctypes.byref(self._a),
                                        self.ws.data_ptr(), _lib.stream_of(x.device)),
                'dq_mlp_forward')
+    if self.dueling:
+      ops.dueling_forward(self.acts['head'], self.A, self.N, out=self.acts['out'])
     return self.acts['out']
 
   def backward(self, dout):
-    """dout: (B, n_out) = d loss / d output of the last ``forward``.  Writes all parameter
-    gradients into net.fp.grad."""
-    assert dout.numel() == self.B * self.n_out and dout.is_contiguous()
+    """dout: d loss / d output of the last ``forward``, shaped as that output.  Writes all
+    parameter gradients into net.fp.grad."""
+    assert dout.numel() == self.acts['out'].numel() and dout.is_contiguous()
     assert dout.dtype == torch.float32
+    if self.dueling:
+      dout = ops.dueling_backward(dout.view(self.B, -1), self.A, self.N, out=self.dhead)
     _lib.check(_lib.lib.dq_mlp_backward(ctypes.byref(self._p), ctypes.byref(self._g), self.B,
                                         ctypes.byref(self._a), dout.data_ptr(),
                                         ctypes.byref(self._d), self.ws.data_ptr(),

@@ -192,6 +192,36 @@ def qr_loss(online_q, target_q, actions, rewards, terminals, cumulative_gamma, k
   return out
 
 
+def dueling_forward(head, num_actions, num_atoms, out=None):
+  """The dueling head's combine (dq_dueling_forward): head (B, (A + 1) * N) -- the advantage
+  stream adv[b, a, z] in columns [0, A * N), the value stream val[b, z] after it -- to
+  out[b, a, z] = (adv - mean_a adv) + val, (B, A * N) (a new tensor, or ``out``)."""
+  A, N = int(num_actions), int(num_atoms)
+  f32 = torch.float32
+  B = head.shape[0]
+  assert head.numel() == B * (A + 1) * N, (tuple(head.shape), A, N)
+  if out is None:
+    out = torch.empty((B, A * N), dtype=f32, device=head.device)
+  assert out.numel() == B * A * N, (tuple(out.shape), B, A, N)
+  _lib.call('dq_dueling_forward', p(_c(head, f32)), B, A, N, p(_c(out, f32)), _stream(head))
+  return out
+
+
+def dueling_backward(dout, num_actions, num_atoms, out=None):
+  """dq_dueling_backward: dout = d loss / d (the combined head), B * A * N values with the
+  sample first, to d loss / d head = [dout - sum_a dout / A | sum_a dout], (B, (A + 1) * N)
+  (a new tensor, or ``out``)."""
+  A, N = int(num_actions), int(num_atoms)
+  f32 = torch.float32
+  B = dout.shape[0]
+  assert dout.numel() == B * A * N, (tuple(dout.shape), A, N)
+  if out is None:
+    out = torch.empty((B, (A + 1) * N), dtype=f32, device=dout.device)
+  assert out.numel() == B * (A + 1) * N, (tuple(out.shape), B, A, N)
+  _lib.call('dq_dueling_backward', p(_c(dout, f32)), B, A, N, p(_c(out, f32)), _stream(dout))
+  return out
+
+
 class TF1Adam(object):
   """tf.train.AdamOptimizer over one flat fp32 buffer (ApplyAdam semantics)."""
 

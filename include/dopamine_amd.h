@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define DQ_ABI_VERSION 13
+#define DQ_ABI_VERSION 14
 
 /* host-side return codes */
 #define DQ_OK 0
@@ -373,6 +373,31 @@ int dq_qr_loss(const float* online_q, const float* target_q, const float* select
                const float* probs, int32_t batch, int32_t num_actions, int32_t num_quantiles,
                float cumulative_gamma, float kappa, float* grad, float* loss_out,
                float* priorities_out, float* mean_loss_out, void* stream);
+
+/* The dueling head (Wang et al., ICML 2016, eq. 9; upstream Dopamine's FullRainbowNetwork)
+ * between a network's last layer and the loss entry points above (ABI 14).  head is the last
+ * layer's output, (B, (A + 1) * N) float32 row-major; N = 1 is the DQN head, N = num_atoms the
+ * Rainbow head (logits for dq_c51_loss*, quantile values for dq_qr_loss).  Columns [0, A * N)
+ * are the advantage stream adv[b, a, z], z fastest; columns [A * N, (A + 1) * N) the value
+ * stream val[b, z]:
+ *   s[b, z]      = ((adv[b, 0, z] + adv[b, 1, z]) + adv[b, 2, z]) + ...   action order
+ *   m[b, z]      = s[b, z] / A                                            one rounded quotient
+ *   out[b, a, z] = (adv[b, a, z] - m[b, z]) + val[b, z]                   (B, A, N)
+ * dq_dueling_backward is its transpose on dout = d loss / d out, (B, A, N):
+ *   dval[b, z]    = ((dout[b, 0, z] + dout[b, 1, z]) + dout[b, 2, z]) + ...
+ *   dadv[b, a, z] = dout[b, a, z] - dval[b, z] / A
+ *   dhead         = [dadv | dval]                                         (B, (A + 1) * N)
+ * One launch each (k_dueling_fwd / k_dueling_bwd), every element of out / dhead written,
+ * nothing read or written outside the B samples.  fp32 in exactly the orders above (a
+ * division, never a reciprocal multiply), no atomics: two calls on the same input are bitwise
+ * equal, and a float32 loop in the same order reproduces them bit for bit.
+ * Limits: 1 <= num_actions <= 64, 1 <= num_atoms <= 256 (the loss kernels'), batch >= 1,
+ * non-NULL pointers, and the output may not be the input.  Anything else is DQ_E_ARG before a
+ * launch, with nothing written. */
+int dq_dueling_forward(const float* head, int32_t batch, int32_t num_actions, int32_t num_atoms,
+                       float* out, void* stream);
+int dq_dueling_backward(const float* dout, int32_t batch, int32_t num_actions,
+                        int32_t num_atoms, float* dhead, void* stream);
 
 /* tf.train.AdamOptimizer.apply_gradients over ONE flat fp32 parameter buffer.
  * state = {beta1_power, beta2_power}[2] (float32, device; slot 0 initialised to

@@ -163,6 +163,14 @@ CASES = {
     'double_quantile_cartpole_mlp': lambda: digest(
         gym('quantile/configs/double_quantile_cartpole.gin')),
     'quantile_acrobot_mlp': lambda: digest(gym('quantile/configs/quantile_acrobot.gin')),
+    # dueling heads (dq_dueling_forward / _backward): a Nature-CNN schedule and the configs
+    'dueling_rainbow_loop': lambda: digest(loop(rainbow(dueling=True))),
+    'dueling_rainbow_cartpole_mlp': lambda: digest(
+        gym('rainbow/configs/dueling_rainbow_cartpole.gin')),
+    'dueling_double_dqn_acrobot_mlp': lambda: digest(
+        gym('dqn/configs/dueling_double_dqn_acrobot.gin')),
+    'dueling_quantile_cartpole_mlp': lambda: digest(
+        gym('quantile/configs/dueling_quantile_cartpole.gin')),
 }
 for _zero in (False, True):
   for _native in (True, False):

@@ -18,7 +18,9 @@ smallest HIP / PyTorch pair ratio and the A/A difference.
 dqn_acrobot_fourier / dqn_cartpole_fourier (the Fourier-basis networks on fourier.hip),
 double_dqn_acrobot / double_rainbow_cartpole (the double-DQN configs: name the plain config
 too for the flag's cost in the same session), c51_cartpole_201 / c51_cartpole_201+double and
-quantile_cartpole / double_quantile_cartpole / quantile_acrobot (QR-DQN, 200 quantiles).
+quantile_cartpole / double_quantile_cartpole / quantile_acrobot (QR-DQN, 200 quantiles) and
+dueling_double_dqn_acrobot / dueling_rainbow_cartpole / dueling_quantile_cartpole (the dueling
+heads; their parents are double_dqn_acrobot / double_rainbow_cartpole / quantile_cartpole).
 --profile-arm runs 300 learner steps and 300 agent steps of the HIP arm only, of every config
 named (the run to put under a kernel-trace profiler for the per-launch table)."""
 import argparse
@@ -60,6 +62,14 @@ for _n in ('quantile_cartpole', 'double_quantile_cartpole', 'quantile_acrobot'):
 # (uniform weights: the loss kernel's instantiation without probabilities, for --profile-arm)
 CONFIGS['quantile_cartpole+uniform'] = CONFIGS['quantile_cartpole'] + (
     ["QuantileAgent.replay_scheme = 'uniform'"],)
+# the dueling heads (dq_dueling_forward / _backward): name the parent config too for the head's
+# cost in the same session
+CONFIGS['dueling_double_dqn_acrobot'] = (
+    os.path.join(_AGENTS, 'dqn', 'configs', 'dueling_double_dqn_acrobot.gin'), 'DQNAgent')
+CONFIGS['dueling_rainbow_cartpole'] = (
+    os.path.join(_AGENTS, 'rainbow', 'configs', 'dueling_rainbow_cartpole.gin'), 'RainbowAgent')
+CONFIGS['dueling_quantile_cartpole'] = (
+    os.path.join(_AGENTS, 'quantile', 'configs', 'dueling_quantile_cartpole.gin'), 'QuantileAgent')
 DEFAULT_CONFIGS = ['rainbow_cartpole', 'dqn_cartpole']
 
 
