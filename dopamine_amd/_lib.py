@@ -9,7 +9,7 @@ import os
 from dopamine_amd import _build
 from dopamine_amd._build import HEADER, LIB_PATH  # noqa: F401
 
-ABI_VERSION = 14
+ABI_VERSION = 15
 OK = 0
 (ST_OK, ST_EMPTY_TREE, ST_MAX_ATTEMPTS, ST_TAPE_EXHAUSTED, ST_NEG_PRIORITY, ST_TOO_FEW, ST_BAD_INDEX,
  ST_BROADCAST) = range(8)
@@ -269,6 +269,11 @@ SIGNATURES = {
     'dq_iqn_workspace_floats': [_I32, _I32, _I32, _I32],
     'dq_uniform_draw': [_P, ctypes.c_uint64, _I64, _P, _P],
     'dq_iqn_tau_cos': [_P, ctypes.c_uint64, _I32, _I32, _P, _P, _P],
+    'dq_noisy_draw': [_P, ctypes.c_uint64, _I64, _P, _P],
+    'dq_noisy_weights': [ctypes.POINTER(MlpParams), ctypes.POINTER(MlpParams), _P,
+                         ctypes.POINTER(MlpParams), _P],
+    'dq_noisy_grads': [ctypes.POINTER(MlpParams), ctypes.POINTER(MlpParams),
+                       ctypes.POINTER(MlpParams), _P, _P],
     'dq_comm_unique_id': [_P],
     'dq_comm_create': [_P, _I32, _I32, _I32, ctypes.POINTER(_P)],
     'dq_comm_destroy': [_P],

@@ -98,6 +98,8 @@ class DQNAgent(object):
                native_comm=True,
                exchange='collective',
                double_dqn=False,
+               noisy=False,
+               noisy_sigma0=0.5,
                dueling=False):
     assert num_actions is not None
     assert isinstance(observation_shape, tuple)      # abstract_agent.py:34
@@ -166,6 +168,30 @@ class DQNAgent(object):
                                                                  networks.FourierDQNNetwork):
       raise ValueError('dueling needs a network with a dense last layer; the Fourier-basis '
                        'networks take no dueling head')
+    # Noisy layers (Fortunato et al. 2018, factorised Gaussian noise): every dense layer of the
+    # classic-control MLPs has mu and sigma parameters and runs on w = mu + sigma * (f_out f_in^T)
+    # with fresh noise per forward.  Three generators per agent (mlp.NoiseSampler), each with a
+    # call counter on the device: 'online' (the online forward, then double_dqn's select forward
+    # on s': two calls, independent noise), 'target' (both pipeline slots' executors) and 'act'
+    # (the batch-1 executor), so no two launches race on a counter even when a target prefetch
+    # runs on the side stream beside an acting forward.  A discarded prefetch is not rewound: it
+    # has consumed a call.  eval_mode acts on the mu network.
+    self.noisy, self.noisy_sigma0 = bool(noisy), float(noisy_sigma0)
+    if self.noisy:
+      if not self.noisy_sigma0 > 0:
+        raise ValueError('noisy_sigma0 must be > 0, got %r' % (noisy_sigma0,))
+      if process_group is not None:
+        raise ValueError('noisy is not supported with data-parallel learners (process_group)')
+      if isinstance(network, type) and issubclass(network, networks.FourierDQNNetwork):
+        raise ValueError('noisy needs dense layers; the Fourier-basis networks take no noisy '
+                         'layers')
+      if not (isinstance(network, type) and
+              issubclass(network, networks.BasicDiscreteDomainNetwork)):
+        # the Nature CNN's fused optimizer and fc2-partials schedules read fc1 / fc2 in place
+        raise ValueError('noisy needs a classic-control MLP network (gym_lib); noisy fc layers '
+                         'on the Nature CNN are not supported')
+    self._noise = None             # noisy: role -> mlp.NoiseSampler
+    self._noise_bufs = {}          # noisy, the PyTorch paths: key -> that forward's noise tensor
     self._online_next = None       # double_dqn: the online network's forward-only executor on s'
     self._peer = None
     self._dp = None                # N > 1: the collective exchange (data_parallel.Exchange)
@@ -338,6 +364,17 @@ class DQNAgent(object):
       exe = self._hip or self._mlp
       d['online_head_out'] = (exe['online'].acts['head'] if exe is not None
                               else self._last_online_head)
+    if self.noisy:                   # the noise each of the step's forwards ran on
+      if self._mlp is not None:
+        d['online_noise'] = self._mlp['online'].acts['noise']
+        d['target_noise'] = self._mlp['target'][c].acts['noise']
+        if self._double():
+          d['online_next_noise'] = self._online_next.acts['noise']
+      else:
+        d['online_noise'] = self._noise_bufs['online']
+        d['target_noise'] = self._noise_bufs['target%d' % c]
+        if self._double():
+          d['online_next_noise'] = self._noise_bufs['online_next']
     return d
 
   def _trace_step(self, slot, c):
@@ -367,20 +404,26 @@ class DQNAgent(object):
   def _network_kwargs(self):
     """Constructor arguments only some networks take (a custom network without a ``dueling``
     argument is constructed as before)."""
-    return {'dueling': True} if self.dueling else {}
+    kw = {'dueling': True} if self.dueling else {}
+    if self.noisy:
+      kw.update(noisy=True, noisy_sigma0=self.noisy_sigma0)
+    return kw
 
   def _is_gym_network(self):
     return (isinstance(self.network, type) and
             issubclass(self.network, (networks.BasicDiscreteDomainNetwork,
                                       networks.FourierDQNNetwork)))
 
-  def _mlp_executor(self, net, batch_size, keep):
+  def _mlp_executor(self, net, batch_size, keep, role='online'):
     """The HIP executor of a classic-control network at this batch size: HipFourier for the
-    Fourier-basis networks (keep: its forward stores what the backward reads), else HipMLP."""
+    Fourier-basis networks (keep: its forward stores what the backward reads), else HipMLP
+    (role: the noise generator a noisy network's executor draws from)."""
     if isinstance(net, networks.FourierDQNNetwork):
       from dopamine_amd.fourier import HipFourier
       return HipFourier(net, batch_size, keep=keep)
     from dopamine_amd.mlp import HipMLP
+    if self.noisy:
+      return HipMLP(net, batch_size, sampler=self._noise[role])
     return HipMLP(net, batch_size)
 
   def _build_mlp(self):
@@ -395,7 +438,8 @@ class DQNAgent(object):
                        % (self.network,))
     B = self._batch_size
     return dict(online=self._mlp_executor(self.online_convnet, B, True),
-                target=[self._mlp_executor(self.target_convnet, B, False) for _ in range(2)])
+                target=[self._mlp_executor(self.target_convnet, B, False, 'target')
+                        for _ in range(2)])
 
   # double_dqn is this class's to carry out (the executor, the loss entry, the schedule);
   # ImplicitQuantileAgent, which has its own double-DQN path, turns it off
@@ -422,9 +466,32 @@ class DQNAgent(object):
     if self._online_next is not None:
       return self._online_next.forward(x)
     with torch.no_grad():
-      return self.online_convnet(self._state_input(x))
+      noise = self._torch_noise('online', 'online_next')
+      return self.online_convnet(self._state_input(x), **noise)
+
+  # the noise generators' seeds: NOISE_SEED + 256 * the agent's seed + the role's index
+  NOISE_SEED = 0x4E015E00
+  NOISE_ROLES = ('online', 'target', 'act')
+
+  def _build_noise(self):
+    from dopamine_amd.mlp import NoiseSampler
+    return {r: NoiseSampler(self.NOISE_SEED + 256 * int(self._seed) + i, self._device)
+            for i, r in enumerate(self.NOISE_ROLES)}
+
+  def _torch_noise(self, role, key):
+    """The PyTorch paths' noise: {} for a plain network, else {'noise': tensor} -- ``key``'s
+    persistent tensor, filled by a fresh draw of ``role``'s generator (the one the HIP
+    executors draw from), for ``network(x, noise=...)``."""
+    if not self.noisy:
+      return {}
+    if key not in self._noise_bufs:
+      self._noise_bufs[key] = torch.empty(self.online_convnet.noise_numel, dtype=torch.float32,
+                                          device=self._device)
+    return {'noise': self._noise[role].draw(self._noise_bufs[key])}
 
   def _build_networks(self):
+    if self.noisy:
+      self._noise = self._build_noise()
     self.online_convnet = self._make_network(self._seed)
     self.target_convnet = self._make_network(self._seed + 1)
     self._mlp = self._build_mlp()
@@ -449,11 +516,12 @@ class DQNAgent(object):
       return self._hip['online'].forward(x)
     if self._mlp is not None:
       return self._mlp['online'].forward(x)
+    noise = self._torch_noise('online', 'online')
     if self.dueling:                    # the PyTorch path: the raw head kept for the trace
-      head = self.online_convnet.head(self._state_input(x))
+      head = self.online_convnet.head(self._state_input(x), **noise)
       self._last_online_head = head.detach()
       return self.online_convnet._combine(head)
-    return self.online_convnet(self._state_input(x))
+    return self.online_convnet(self._state_input(x), **noise)
 
   def _target_net(self, x, slot):
     """Target network output (no gradient) into pipeline slot ``slot``."""
@@ -462,7 +530,8 @@ class DQNAgent(object):
     if self._mlp is not None:
       return self._mlp['target'][slot].forward(x)
     with torch.no_grad():
-      return self.target_convnet(self._state_input(x))
+      noise = self._torch_noise('target', 'target%d' % slot)
+      return self.target_convnet(self._state_input(x), **noise)
 
   def _build_train_op(self):
     B, A, dev = self._batch_size, self.num_actions, self._device
@@ -1123,20 +1192,21 @@ class DQNAgent(object):
     return out
 
   def _online_q(self, x):
-    return self._q_from_output(self.online_convnet(x))
+    noise = {} if self.eval_mode else self._torch_noise('act', 'act')
+    return self._q_from_output(self.online_convnet(x, **noise))
 
-  def _act_graph(self, exe, x):
-    """(graph, its Q-values tensor): a batch-1 executor's forward on x and the Q reduction,
-    warmed up on a stream of its own and captured."""
+  def _act_graph(self, exe, x, **kw):
+    """(graph, its Q-values tensor): a batch-1 executor's forward on x (kw: its other
+    arguments) and the Q reduction, warmed up on a stream of its own and captured."""
     main = torch.cuda.current_stream(self._device)
     warm = torch.cuda.Stream(self._device)
     warm.wait_stream(main)
     with torch.cuda.stream(warm):
-      self._q_from_output(exe.forward(x))
+      self._q_from_output(exe.forward(x, **kw))
     main.wait_stream(warm)
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g):
-      q = self._q_from_output(exe.forward(x))
+      q = self._q_from_output(exe.forward(x, **kw))
     return g, q
 
   def _act_q(self, state_np):
@@ -1161,6 +1231,8 @@ class DQNAgent(object):
     forward's launches and the Q reduction are one captured graph (use_hip_graph), the state
     goes up through a pinned staging buffer in the observation's own dtype and is cast to
     float32 in the first kernel.  (stack_size 1: the flattened state is the observation.)"""
+    if self.noisy:
+      return self._act_q_noisy(state_np)
     if self._act is None:
       exe = self._mlp_executor(self.online_convnet, 1, False)
       dt = torch.float32 if np.dtype(self.observation_dtype) == np.float32 else torch.float64
@@ -1172,6 +1244,28 @@ class DQNAgent(object):
     x.copy_(pin, non_blocking=True)
     if g is None:
       return self._q_from_output(exe.forward(x))
+    g.replay()
+    return q
+
+  def _act_q_noisy(self, state_np):
+    """_act_q_mlp on a noisy network: one cached executor and graph per ``eval_mode`` value
+    (the runner flips it between phases) -- training acts on a fresh draw of the 'act'
+    generator per call, evaluation on the mu network, with no launch added."""
+    noise = not self.eval_mode
+    if self._act is None:
+      self._act = {}
+    if noise not in self._act:
+      exe = self._mlp_executor(self.online_convnet, 1, False, 'act')
+      dt = torch.float32 if np.dtype(self.observation_dtype) == np.float32 else torch.float64
+      x = torch.zeros(exe.D, dtype=dt, device=self._device)
+      pin = torch.empty(exe.D, dtype=dt).pin_memory()
+      graph = self._act_graph(exe, x, noise=noise) if self.use_hip_graph else (None, None)
+      self._act[noise] = (exe, x, pin) + graph
+    exe, x, pin, g, q = self._act[noise]
+    pin.numpy()[:] = np.asarray(state_np).reshape(-1)
+    x.copy_(pin, non_blocking=True)
+    if g is None:
+      return self._q_from_output(exe.forward(x, noise=noise))
     g.replay()
     return q
 
@@ -1431,6 +1525,8 @@ class DQNAgent(object):
   def _ckpt_tensors(self):
     d = {'online': self.online_convnet.fp.flat, 'target': self.target_convnet.fp.flat}
     d.update(('opt_' + k, v) for k, v in self._opt_tensors())    # the file's keys: a format
+    if self.noisy:     # the generators' call counters: a resumed run continues the noise streams
+      d.update(('noise_' + r, s.counter) for r, s in self._noise.items())
     return d
 
   def _rank_dir(self, checkpoint_dir):

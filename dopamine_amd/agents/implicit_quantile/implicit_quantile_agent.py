@@ -36,7 +36,11 @@ class ImplicitQuantileAgent(rainbow_agent.RainbowAgent):
                summary_writer=None,
                summary_writing_frequency=500,
                dueling=False,
+               noisy=False,
                **kwargs):
+    if noisy:
+      # the implicit-quantile head (iqn.hip) has no noisy form
+      raise ValueError('ImplicitQuantileAgent has no noisy layers (noisy=True)')
     if dueling:
       # the IQN head's output is (N * B, A), one row per sampled quantile, and upstream's
       # implicit-quantile network has no dueling form

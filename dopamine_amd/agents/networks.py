@@ -116,10 +116,15 @@ class _Net(object):
 
   tail_align = None
   dueling = False
+  noisy = False
 
   def __init__(self, device, seed, init='rainbow'):
     self.fp = FlatParams(self.shapes(), device, self.tail_align)
     gen = torch.Generator().manual_seed(seed)
+    if self.noisy:          # noisy layers have an initialisation of their own
+      with torch.no_grad():
+        self._init_noisy(gen, device)
+      return
     with torch.no_grad():
       for name, (o, shape) in self.fp.offsets.items():
         if name.endswith('_b'):
@@ -271,15 +276,20 @@ class BasicDiscreteDomainNetwork(_Net):
   linear layer of num_actions (Q-values) or num_actions * num_atoms (C51 logits) outputs.
   Xavier-uniform weights, zero biases (slim's defaults).  ``forward`` is the PyTorch path
   (``use_hip_mlp=False``); dopamine_amd.mlp.HipMLP runs the same parameters on the HIP
-  kernels."""
+  kernels.  ``noisy``: factorised-Gaussian noisy layers (Fortunato et al. 2018) -- the names
+  above hold mu, a sigma pair per layer follows them all (``shapes``), ``head(x, noise)`` runs
+  on mu + sigma * noise and the initialisation is the paper's (``_init_noisy``)."""
 
   MIN = MAX = None      # the domain's observation bounds (float64), set by subclasses
   GIN_NAME = None       # the reference's configurable, whose network_size binding is honoured
   HEAD = 'out'
 
   def __init__(self, num_actions, num_atoms=None, stack_size=1, device='cuda', seed=0,
-               network_size=None, dueling=False):
+               network_size=None, dueling=False, noisy=False, noisy_sigma0=0.5):
     self.dueling = bool(dueling)
+    self.noisy, self.noisy_sigma0 = bool(noisy), float(noisy_sigma0)
+    if self.noisy and not self.noisy_sigma0 > 0:
+      raise ValueError('noisy_sigma0 must be > 0, got %r' % (noisy_sigma0,))
     if network_size is None:    # the gin binding (acrobot_dqn_network.network_size), or 512-512
       bound = gin_lite.query(self.GIN_NAME) if self.GIN_NAME else {}
       network_size = bound.get('network_size', (512, 512))
@@ -295,20 +305,70 @@ class BasicDiscreteDomainNetwork(_Net):
     """The last layer's rows: A * N, or with ``dueling`` (A + 1) * N (the value stream last)."""
     return (self.A + int(self.dueling)) * (self.N or 1)
 
-  def shapes(self):
-    dims = [self.D] + list(self.sizes)
-    s = []
-    for i in range(len(self.sizes)):
-      s += [('fc%d_w' % i, (dims[i + 1], dims[i])), ('fc%d_b' % i, (dims[i + 1],))]
-    return s + [('out_w', (self.n_out, dims[-1])), ('out_b', (self.n_out,))]
+  def layer_names(self):
+    return ['fc%d' % i for i in range(len(self.sizes))] + ['out']
 
-  def head(self, x):
-    """The last layer's raw output (B, n_out)."""
+  def shapes(self):
+    """The layers' weights and biases -- with ``noisy`` the mu parameters -- then, with
+    ``noisy``, every layer's sigma_w / sigma_b AFTER all of them: the mu offsets are the plain
+    network's, so whatever reads the layers by name (mlp._params_struct) reads mu."""
+    dims = [self.D] + list(self.sizes) + [self.n_out]
+    s = []
+    for i, n in enumerate(self.layer_names()):
+      s += [(n + '_w', (dims[i + 1], dims[i])), (n + '_b', (dims[i + 1],))]
+    if self.noisy:
+      for i, n in enumerate(self.layer_names()):
+        s += [(n + '_sigma_w', (dims[i + 1], dims[i])), (n + '_sigma_b', (dims[i + 1],))]
+    return s
+
+  @property
+  def mu_numel(self):
+    """Floats of the flat buffer's mu region (a plain network: the whole buffer)."""
+    return self.fp.offsets['fc0_sigma_w'][0] if self.noisy else self.fp.numel
+
+  @property
+  def noise_numel(self):
+    """Floats of a noise buffer: [f_in_0 (D) | f_out_0 | f_in_1 | f_out_1 | ...], layer-major."""
+    return self.D + 2 * sum(self.sizes) + self.n_out
+
+  def _init_noisy(self, gen, device):
+    """Fortunato et al. 2018, section 3.2, factorised noise: for a layer of p inputs mu_w and
+    mu_b ~ U(-1 / sqrt(p), 1 / sqrt(p)), sigma_w = sigma_b = sigma0 / sqrt(p).  Drawn layer by
+    layer, mu_w then mu_b.  A dueling last layer is one noisy layer (both blocks share p)."""
+    for n in self.layer_names():
+      w = self.fp[n + '_w']
+      p = w.shape[1]
+      lim = 1.0 / math.sqrt(p)
+      for name in (n + '_w', n + '_b'):
+        t = self.fp[name]
+        t.copy_(((torch.rand(tuple(t.shape), generator=gen) * 2 - 1) * lim).to(device))
+      self.fp[n + '_sigma_w'].fill_(self.noisy_sigma0 / math.sqrt(p))
+      self.fp[n + '_sigma_b'].fill_(self.noisy_sigma0 / math.sqrt(p))
+
+  def head(self, x, noise=None):
+    """The last layer's raw output (B, n_out).  noise: a (noise_numel,) tensor of f-transformed
+    normals (the layout above) -- every layer runs on w = mu_w + sigma_w * (f_out f_in^T),
+    b = mu_b + sigma_b * f_out, as a torch expression, so autograd yields the sigma gradients
+    (what dq_noisy_weights / dq_noisy_grads compute on the HIP executor); None: the mu
+    network."""
     h = x.reshape(x.shape[0], -1).float()
     h = 2.0 * ((h - self._min) / self._rng) - 1.0
-    for i in range(len(self.sizes)):
-      h = F.relu(F.linear(h, self.fp['fc%d_w' % i], self.fp['fc%d_b' % i]))
-    return F.linear(h, self.fp['out_w'], self.fp['out_b'])
+    names, off = self.layer_names(), 0
+    for n in names:
+      w, b = self.fp[n + '_w'], self.fp[n + '_b']
+      if noise is not None:
+        q, p = w.shape
+        f_in, f_out = noise[off:off + p], noise[off + p:off + p + q]
+        off += p + q
+        w = w + self.fp[n + '_sigma_w'] * (f_out[:, None] * f_in[None, :])
+        b = b + self.fp[n + '_sigma_b'] * f_out
+      h = F.linear(h, w, b)
+      if n != 'out':
+        h = F.relu(h)
+    return h
+
+  def forward(self, x, noise=None):
+    return self._combine(self.head(x, noise))
 
 
 _CARTPOLE_MIN = np.array([-2.4, -5., -math.pi / 12., -math.pi * 2.])
@@ -324,9 +384,10 @@ class CartpoleDQNNetwork(BasicDiscreteDomainNetwork):
   GIN_NAME = 'cartpole_dqn_network'
 
   def __init__(self, num_actions, device='cuda', seed=0, network_size=None, num_atoms=None,
-               stack_size=1, dueling=False):
+               stack_size=1, dueling=False, noisy=False, noisy_sigma0=0.5):
     assert num_atoms is None
-    super().__init__(num_actions, None, stack_size, device, seed, network_size, dueling)
+    super().__init__(num_actions, None, stack_size, device, seed, network_size, dueling, noisy,
+                     noisy_sigma0)
 
 
 class CartpoleRainbowNetwork(BasicDiscreteDomainNetwork):
@@ -336,8 +397,9 @@ class CartpoleRainbowNetwork(BasicDiscreteDomainNetwork):
   GIN_NAME = 'cartpole_rainbow_network'
 
   def __init__(self, num_actions, num_atoms=51, stack_size=1, device='cuda', seed=0,
-               network_size=None, dueling=False):
-    super().__init__(num_actions, num_atoms, stack_size, device, seed, network_size, dueling)
+               network_size=None, dueling=False, noisy=False, noisy_sigma0=0.5):
+    super().__init__(num_actions, num_atoms, stack_size, device, seed, network_size, dueling,
+                     noisy, noisy_sigma0)
 
 
 class AcrobotDQNNetwork(BasicDiscreteDomainNetwork):
@@ -347,9 +409,10 @@ class AcrobotDQNNetwork(BasicDiscreteDomainNetwork):
   GIN_NAME = 'acrobot_dqn_network'
 
   def __init__(self, num_actions, device='cuda', seed=0, network_size=None, num_atoms=None,
-               stack_size=1, dueling=False):
+               stack_size=1, dueling=False, noisy=False, noisy_sigma0=0.5):
     assert num_atoms is None
-    super().__init__(num_actions, None, stack_size, device, seed, network_size, dueling)
+    super().__init__(num_actions, None, stack_size, device, seed, network_size, dueling, noisy,
+                     noisy_sigma0)
 
 
 class AcrobotRainbowNetwork(BasicDiscreteDomainNetwork):
@@ -359,8 +422,9 @@ class AcrobotRainbowNetwork(BasicDiscreteDomainNetwork):
   GIN_NAME = 'acrobot_rainbow_network'
 
   def __init__(self, num_actions, num_atoms=51, stack_size=1, device='cuda', seed=0,
-               network_size=None, dueling=False):
-    super().__init__(num_actions, num_atoms, stack_size, device, seed, network_size, dueling)
+               network_size=None, dueling=False, noisy=False, noisy_sigma0=0.5):
+    super().__init__(num_actions, num_atoms, stack_size, device, seed, network_size, dueling,
+                     noisy, noisy_sigma0)
 
 
 def fourier_multipliers(in_dim, order):

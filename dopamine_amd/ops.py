@@ -222,6 +222,31 @@ def dueling_backward(dout, num_actions, num_atoms, out=None):
   return out
 
 
+def noisy_draw(counter, seed, out):
+  """dq_noisy_draw: out (float32, any shape) <- f(n_i) = sgn(n_i) sqrt(|n_i|) of the standard
+  normals of call counter[0] of generator ``seed``; then counter[0] += 1 in the same launch
+  (counter: two int64 on the device, the call count and the launch's block ticket)."""
+  assert counter.dtype == torch.int64 and counter.numel() == 2 and counter.is_cuda
+  _lib.call('dq_noisy_draw', p(counter), ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
+            out.numel(), p(_c(out, torch.float32)), _stream(out))
+  return out
+
+
+def noisy_weights(mu, sigma, noise, eff):
+  """dq_noisy_weights: every layer's w = mu_w + sigma_w * (f_out f_in^T), b = mu_b + sigma_b *
+  f_out in one launch.  mu, sigma, eff: _lib.MlpParams of one geometry over three buffers;
+  noise: the network's noise buffer [f_in_0 | f_out_0 | f_in_1 | ...]."""
+  _lib.call('dq_noisy_weights', ctypes.byref(mu), ctypes.byref(sigma),
+            p(_c(noise, torch.float32)), ctypes.byref(eff), _stream(noise))
+
+
+def noisy_grads(geometry, g_mu, g_sigma, noise):
+  """dq_noisy_grads: d sigma_w = d mu_w * (f_out f_in^T), d sigma_b = d mu_b * f_out for every
+  layer in one launch (the mu gradients are what dq_mlp_backward wrote)."""
+  _lib.call('dq_noisy_grads', ctypes.byref(geometry), ctypes.byref(g_mu), ctypes.byref(g_sigma),
+            p(_c(noise, torch.float32)), _stream(noise))
+
+
 class TF1Adam(object):
   """tf.train.AdamOptimizer over one flat fp32 buffer (ApplyAdam semantics)."""
 

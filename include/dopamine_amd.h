@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define DQ_ABI_VERSION 14
+#define DQ_ABI_VERSION 15
 
 /* host-side return codes */
 #define DQ_OK 0
@@ -736,6 +736,41 @@ int dq_uniform_draw(int64_t* counter, uint64_t seed, int64_t n, float* out, void
    dq_iqn_head_forward with taus NULL: two launches instead of three. */
 int dq_iqn_tau_cos(int64_t* counter, uint64_t seed, int32_t rows, int32_t embed_dim, float* taus,
                    float* cos_out, void* stream);
+
+/* ---------------- factorised-Gaussian noisy layers for the classic-control MLP (ABI 15) ----
+ * NoisyNet (Fortunato et al., ICLR 2018, section 3 (b), eq. 10-11).  A dense layer of p inputs
+ * and q outputs has mu_w (q, p), mu_b (q), sigma_w (q, p), sigma_b (q) and noise f_in (p),
+ * f_out (q), f(n) = sgn(n) sqrt(|n|) of standard normals n:
+ *   e[j, k] = f_out[j] * f_in[k]
+ *   w[j, k] = mu_w[j, k] + sigma_w[j, k] * e[j, k]      b[j] = mu_b[j] + sigma_b[j] * f_out[j]
+ *   d sigma_w = dw * e      d sigma_b = db * f_out      (d mu = dw, db: dq_mlp_backward's)
+ * A network's noise buffer is layer-major, [f_in_0 (in_dim) | f_out_0 | f_in_1 | f_out_1 | ...]
+ * (in_dim + 2 * the widths + n_out values), and element i of it is draw i of one generator call.
+ *
+ * dq_noisy_draw: out[i] = f(n_i), i < n, of call counter[0] of generator `seed`, then
+ * counter[0] += 1 inside the same launch (a last-block ticket on counter[1], which is zero
+ * between launches: counter is two int64), so graph replays continue the eager sequence.
+ * Draw i of call c: z = dq_uniform_draw's splitmix64 hash of (seed, c, i + 1);
+ *   u1 = ((z >> 40) + 1) * 2^-24 in (0, 1], u2 = ((z >> 16) & 0xFFFFFF) * 2^-24,
+ *   n = sqrt(-2 ln u1) * cos(2 pi u2)  (Box-Muller; the cosine as cospi(2 u2)).
+ * One launch; 1 <= n <= 2^31.
+ *
+ * dq_noisy_weights: eff = the w and b above for every layer, one launch, fp32 in exactly this
+ * order: e = f_out * f_in (one rounded product), then mu + (sigma * e), a rounded product and a
+ * rounded sum, never contracted: a float32 loop reproduces eff bit for bit from the noise.
+ * mu, sigma and eff are dq_mlp_params of one geometry over three buffers (in_min / in_range
+ * are not read); only the layers' own elements are written, never a slice's padding.
+ *
+ * dq_noisy_grads: g_sigma = g_mu * e (weights; e by the same product) and g_mu * f_out (biases),
+ * one launch; `geometry` gives the sizes (its pointers are not read).
+ *
+ * Limits: dq_mlp_params' own; non-NULL, 16-byte aligned pointers; eff may not alias mu or
+ * sigma, nor g_sigma g_mu.  Anything else is DQ_E_ARG before a launch, with nothing written. */
+int dq_noisy_draw(int64_t* counter, uint64_t seed, int64_t n, float* out, void* stream);
+int dq_noisy_weights(const dq_mlp_params* mu, const dq_mlp_params* sigma, const float* noise,
+                     const dq_mlp_params* eff, void* stream);
+int dq_noisy_grads(const dq_mlp_params* geometry, const dq_mlp_params* g_mu,
+                   const dq_mlp_params* g_sigma, const float* noise, void* stream);
 
 /* _build_sync_op (dqn_agent.py:324-339): online -> target copy of the flat buffer. */
 int dq_sync_copy(void* dst, const void* src, int64_t bytes, void* stream);

@@ -171,6 +171,11 @@ CASES = {
         gym('dqn/configs/dueling_double_dqn_acrobot.gin')),
     'dueling_quantile_cartpole_mlp': lambda: digest(
         gym('quantile/configs/dueling_quantile_cartpole.gin')),
+    # noisy layers (dq_noisy_draw / _weights / _grads): the configs
+    'full_rainbow_cartpole_mlp': lambda: digest(gym('rainbow/configs/full_rainbow_cartpole.gin')),
+    'noisy_dqn_acrobot_mlp': lambda: digest(gym('dqn/configs/noisy_dqn_acrobot.gin')),
+    'noisy_quantile_cartpole_mlp': lambda: digest(
+        gym('quantile/configs/noisy_quantile_cartpole.gin')),
 }
 for _zero in (False, True):
   for _native in (True, False):

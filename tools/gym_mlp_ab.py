@@ -20,7 +20,9 @@ double_dqn_acrobot / double_rainbow_cartpole (the double-DQN configs: name the p
 too for the flag's cost in the same session), c51_cartpole_201 / c51_cartpole_201+double and
 quantile_cartpole / double_quantile_cartpole / quantile_acrobot (QR-DQN, 200 quantiles) and
 dueling_double_dqn_acrobot / dueling_rainbow_cartpole / dueling_quantile_cartpole (the dueling
-heads; their parents are double_dqn_acrobot / double_rainbow_cartpole / quantile_cartpole).
+heads; their parents are double_dqn_acrobot / double_rainbow_cartpole / quantile_cartpole) and
+noisy_dqn_acrobot / full_rainbow_cartpole / noisy_quantile_cartpole (the noisy layers; their
+parents are dqn_acrobot / dueling_rainbow_cartpole / quantile_cartpole).
 --profile-arm runs 300 learner steps and 300 agent steps of the HIP arm only, of every config
 named (the run to put under a kernel-trace profiler for the per-launch table)."""
 import argparse
@@ -70,6 +72,14 @@ CONFIGS['dueling_rainbow_cartpole'] = (
     os.path.join(_AGENTS, 'rainbow', 'configs', 'dueling_rainbow_cartpole.gin'), 'RainbowAgent')
 CONFIGS['dueling_quantile_cartpole'] = (
     os.path.join(_AGENTS, 'quantile', 'configs', 'dueling_quantile_cartpole.gin'), 'QuantileAgent')
+# the noisy layers (dq_noisy_draw / _weights / _grads): name the parent config too for the
+# noise's cost in the same session
+CONFIGS['noisy_dqn_acrobot'] = (
+    os.path.join(_AGENTS, 'dqn', 'configs', 'noisy_dqn_acrobot.gin'), 'DQNAgent')
+CONFIGS['full_rainbow_cartpole'] = (
+    os.path.join(_AGENTS, 'rainbow', 'configs', 'full_rainbow_cartpole.gin'), 'RainbowAgent')
+CONFIGS['noisy_quantile_cartpole'] = (
+    os.path.join(_AGENTS, 'quantile', 'configs', 'noisy_quantile_cartpole.gin'), 'QuantileAgent')
 DEFAULT_CONFIGS = ['rainbow_cartpole', 'dqn_cartpole']
 
 
