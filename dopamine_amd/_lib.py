@@ -9,7 +9,7 @@ import os
 from dopamine_amd import _build
 from dopamine_amd._build import HEADER, LIB_PATH  # noqa: F401
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 OK = 0
 (ST_OK, ST_EMPTY_TREE, ST_MAX_ATTEMPTS, ST_TAPE_EXHAUSTED, ST_NEG_PRIORITY, ST_TOO_FEW, ST_BAD_INDEX,
  ST_BROADCAST) = range(8)
@@ -201,6 +201,7 @@ SIGNATURES = {
     'dq_c51_loss_double': [_P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _F, _P, _P, _P, _P,
                            _P],
     'dq_dqn_huber_loss_double': [_P, _P, _P, _P, _P, _P, _I32, _I32, _F, _P, _P, _P, _P],
+    'dq_mdqn_loss': [_P, _P, _P, _P, _P, _P, _I32, _I32, _F, _F, _F, _F, _P, _P, _P, _P],
     'dq_iqn_loss': [_P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _F, _F, _P, _P, _P, _P],
     'dq_qr_loss': [_P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _F, _F, _P, _P, _P, _P, _P],
     'dq_dueling_forward': [_P, _I32, _I32, _I32, _P, _P],

@@ -100,6 +100,10 @@ class DQNAgent(object):
                double_dqn=False,
                noisy=False,
                noisy_sigma0=0.5,
+               munchausen=False,
+               munchausen_tau=0.03,
+               munchausen_alpha=0.9,
+               munchausen_clip=-1.0,
                dueling=False):
     assert num_actions is not None
     assert isinstance(observation_shape, tuple)      # abstract_agent.py:34
@@ -190,6 +194,36 @@ class DQNAgent(object):
         # the Nature CNN's fused optimizer and fc2-partials schedules read fc1 / fc2 in place
         raise ValueError('noisy needs a classic-control MLP network (gym_lib); noisy fc layers '
                          'on the Nature CNN are not supported')
+    # Munchausen-DQN (Vieillard, Pietquin, Geist, NeurIPS 2020): the regression target alone
+    # changes -- max_a' Q'(s', a') becomes the soft value of Q'(s', .) under softmax(. / tau), and
+    # alpha * clip(tau log pi(a | s), clip, 0) of the TARGET network's Q'(s, .) is added to the
+    # reward, once whatever update_horizon is and whether or not the transition is terminal.  The
+    # target network's extra forward on ``state`` runs inside the step (_online_loss), where
+    # double_dqn's extra forward runs.
+    self.munchausen = bool(munchausen)
+    self.munchausen_tau = float(munchausen_tau)
+    self.munchausen_alpha = float(munchausen_alpha)
+    self.munchausen_clip = float(munchausen_clip)
+    if self.munchausen:
+      if not self._base_munchausen:
+        raise ValueError('munchausen is not supported by %s (Munchausen targets for the '
+                         'distributional agents are not implemented)' % type(self).__name__)
+      if double_dqn:
+        raise ValueError('munchausen with double_dqn: a soft value has no greedy action')
+      if self.noisy:
+        # the target network's forward on ``state`` would need a fourth generator and its
+        # checkpoint slot
+        raise ValueError('munchausen is not supported with noisy layers')
+      if process_group is not None:
+        raise ValueError('munchausen is not supported with data-parallel learners '
+                         '(process_group)')
+      if not (math.isfinite(self.munchausen_tau) and self.munchausen_tau > 0):
+        raise ValueError('munchausen_tau must be > 0, got %r' % (munchausen_tau,))
+      if not (math.isfinite(self.munchausen_alpha) and self.munchausen_alpha >= 0):
+        raise ValueError('munchausen_alpha must be >= 0, got %r' % (munchausen_alpha,))
+      if not (math.isfinite(self.munchausen_clip) and self.munchausen_clip <= 0):
+        raise ValueError('munchausen_clip must be <= 0, got %r' % (munchausen_clip,))
+    self._target_cur = None        # munchausen: the target network's forward-only executor on s
     self._noise = None             # noisy: role -> mlp.NoiseSampler
     self._noise_bufs = {}          # noisy, the PyTorch paths: key -> that forward's noise tensor
     self._online_next = None       # double_dqn: the online network's forward-only executor on s'
@@ -360,6 +394,8 @@ class DQNAgent(object):
       d['target_out'] = self._ptgt[c]['q']
     if self._double():               # the online network's output on next_state (select)
       d['online_next_out'] = self._last_online_next.reshape(self._batch_size, -1)
+    if self._munchausen():           # the target network's output on state (the log-policy)
+      d['target_cur_out'] = self._last_target_cur.reshape(self._batch_size, -1)
     if self.dueling:                 # the online network's raw head (the outputs above: combined)
       exe = self._hip or self._mlp
       d['online_head_out'] = (exe['online'].acts['head'] if exe is not None
@@ -469,6 +505,32 @@ class DQNAgent(object):
       noise = self._torch_noise('online', 'online_next')
       return self.online_convnet(self._state_input(x), **noise)
 
+  # munchausen is this class's to carry out, as double_dqn; the distributional agents (Rainbow,
+  # QR-DQN, IQN), whose loss entries take hard greedy targets, turn it off and refuse the flag
+  _base_munchausen = True
+
+  def _munchausen(self):
+    return bool(self.munchausen) and self._base_munchausen
+
+  def _build_target_cur(self):
+    """munchausen: the forward-only executor of the target network on state (it reads the
+    target parameters in place), or None on the PyTorch paths.  A hook, as _build_online_next."""
+    B = self._batch_size
+    if self._hip is not None:
+      from dopamine_amd.cnn import HipNatureCNN
+      return HipNatureCNN(self.target_convnet, B)
+    if self._mlp is not None:
+      return self._mlp_executor(self.target_convnet, B, False, 'target')
+    return None
+
+  def _target_cur_forward(self, x):
+    """The target network's output on state at the parameters as they stand on the step's
+    stream (no gradient)."""
+    if self._target_cur is not None:
+      return self._target_cur.forward(x)
+    with torch.no_grad():
+      return self.target_convnet(self._state_input(x))
+
   # the noise generators' seeds: NOISE_SEED + 256 * the agent's seed + the role's index
   NOISE_SEED = 0x4E015E00
   NOISE_ROLES = ('online', 'target', 'act')
@@ -506,6 +568,8 @@ class DQNAgent(object):
                        target=[HipNatureCNN(self.target_convnet, B) for _ in range(2)])
     if self._double():
       self._online_next = self._build_online_next()
+    if self._munchausen():
+      self._target_cur = self._build_target_cur()
 
   def _online_forward(self, x):
     """Online network output for the loss (keeps what the backward needs)."""
@@ -555,6 +619,12 @@ class DQNAgent(object):
     """dqn_agent.py:283-322."""
     q = self._online_forward(t['state'])
     self._last_online_out = q.detach()
+    if self._munchausen():
+      out = ops.mdqn_loss(q.detach(), tgt['q'], self._target_cur_output(t), t['action'],
+                          t['reward'], t['terminal'], self.cumulative_gamma,
+                          self.munchausen_tau, self.munchausen_alpha, self.munchausen_clip,
+                          out=self._loss_out)
+      return q, out['grad']
     out = ops.dqn_huber_loss(q.detach(), tgt['q'], t['action'], t['reward'], t['terminal'],
                              self.cumulative_gamma, out=self._loss_out,
                              select_q=self._select_output(t))
@@ -570,6 +640,15 @@ class DQNAgent(object):
       return None
     self._last_online_next = self._online_next_forward(t['next_state']).detach()
     return self._last_online_next
+
+  def _target_cur_output(self, t):
+    """munchausen: the target network's output on state, computed here -- in the step, on its
+    stream, after the online forward and before the loss kernel, as _select_output and for its
+    reasons: the target parameters change only at dq_sync_copy on this stream, so eager steps,
+    per-step graphs and chunk graphs all read the parameters the step's other target forward
+    read."""
+    self._last_target_cur = self._target_cur_forward(t['state']).detach()
+    return self._last_target_cur
 
   def _fused_opt(self):
     """fuse_optimizer + single replica + HIP CNN + TF1 Adam or RMSProp: the optimizer
@@ -655,8 +734,10 @@ class DQNAgent(object):
     online network's output on s', so that agent takes fused_head=False's schedule (stored
     outputs, then the plain loss entry).  Nor with dueling: the fused loss kernels sum fc2
     partials of an A * N head, and the combine needs the stored (A + 1) * N outputs, so that
-    agent takes the same stored-outputs schedule."""
-    return self.fused_head and self._rides() and not self._double() and not self.dueling
+    agent takes the same stored-outputs schedule.  Nor with munchausen: the fused DQN head has
+    no third input for the target network's output on s."""
+    return (self.fused_head and self._rides() and not self._double() and not self.dueling and
+            not self._munchausen())
 
   def _fused_loss(self, t, c):
     """_online_loss on the CNN's fc2 partials: Q / Q' summed in the loss kernel

@@ -108,6 +108,9 @@ class RainbowAgent(dqn_agent.DQNAgent):
                      summary_writing_frequency=summary_writing_frequency, **kwargs)
 
   _loss_name = 'CrossEntropyLoss'
+  # Munchausen targets for the distributional losses (C51, QR-DQN, M-IQN) are not implemented:
+  # DQNAgent refuses munchausen=True for this class and its subclasses at construction
+  _base_munchausen = False
 
   def _build_replay_buffer(self, use_staging):
     if self._replay_scheme not in ['uniform', 'prioritized']:

@@ -124,6 +124,26 @@ def dqn_huber_loss(online_q, target_q, actions, rewards, terminals, cumulative_g
   return out
 
 
+def mdqn_loss(online_q, target_next_q, target_cur_q, actions, rewards, terminals,
+              cumulative_gamma, tau, alpha, clip_min, out=None):
+  """Munchausen-DQN's loss (Vieillard et al. 2020; dq_mdqn_loss): dqn_huber_loss with the soft
+  value of target_next_q = Q'(s', .) under softmax(. / tau) in place of its maximum, and
+  alpha * clip(tau log pi(a | s), clip_min, 0) of target_cur_q = Q'(s, .) added to the reward."""
+  B, A = online_q.shape
+  f32 = torch.float32
+  assert target_next_q.shape == online_q.shape and target_cur_q.shape == online_q.shape
+  if out is None:
+    dev = online_q.device
+    out = dict(grad=torch.empty_like(online_q), loss=torch.empty(B, dtype=f32, device=dev),
+               mean_loss=torch.empty(1, dtype=f32, device=dev))
+  _lib.call('dq_mdqn_loss', p(_c(online_q, f32)), p(_c(target_next_q, f32)),
+            p(_c(target_cur_q, f32)), p(_c(actions, torch.int32)), p(_c(rewards, f32)),
+            p(_c(terminals, torch.uint8)), B, A, float(cumulative_gamma), float(tau),
+            float(alpha), float(clip_min), p(out['grad']), p(out['loss']), p(out['mean_loss']),
+            _stream(online_q))
+  return out
+
+
 def dqn_huber_loss_fused(online, target, actions, rewards, terminals, cumulative_gamma, out=None,
                          q_out=False):
   """dqn_huber_loss on the HIP CNN's fc2 k-band partials (cnn.forward_fused) of the

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define DQ_ABI_VERSION 15
+#define DQ_ABI_VERSION 16
 
 /* host-side return codes */
 #define DQ_OK 0
@@ -339,6 +339,33 @@ int dq_dqn_huber_loss_fused(const float* online_parts, const float* online_bias,
                             float cumulative_gamma, float* grad_q, float* loss_out,
                             const float* fc2_w, const float* h, float* dh, int32_t hidden,
                             float* online_q_out, float* target_q_out, void* stream);
+
+/* Munchausen-DQN's loss (Vieillard, Pietquin, Geist, "Munchausen Reinforcement Learning",
+ * NeurIPS 2020, eq. 2 with the clipped log-policy of section 4; the authors' Dopamine agent)
+ * (ABI 16).  online_q = Q(s, .), target_next_q = X' = Q'(s', .), target_cur_q = X = Q'(s, .),
+ * all (B, A) float32.  For a row x:  m = max_j x_j,  S = sum_j expf((x_j - m) / tau),
+ * tau log pi_j = (x_j - m) - tau logf(S).  Per sample, with a the taken action:
+ *   V      = m' + tau logf(S')            = sum_j pi'_j (X'_j - tau log pi'_j), the soft value
+ *   bonus  = alpha * min(max(tau log pi_a(X), clip_min), 0)
+ *   target = (r + bonus) + (gamma^n * V) * (1 - terminal)
+ *   err    = online_q[b, a] - target
+ * then Huber(1), grad_q (B, A) = clip(err, -1, 1) / B on the taken action and zeros elsewhere,
+ * loss_out (B,) and mean_loss_out (1,) = sum loss / B exactly as dq_dqn_huber_loss (both may be
+ * NULL; mean_loss_out needs loss_out).  The bonus is not masked by terminal and is added once
+ * whatever the update horizon.  fp32, every operation rounded once, the maximum subtracted
+ * before every expf: Q of any finite magnitude gives finite outputs, and a row whose gaps are
+ * far above tau gives S = 1 and V = m'.  One launch, no workspace, any batch >= 1 and
+ * num_actions >= 1; S is summed per lane (actions lane, lane + 64, ..) and then across the 64
+ * lanes by an xor butterfly (32, 16, .., 1), the mean in dq_dqn_huber_loss's order: two calls
+ * are bitwise equal, and with num_actions = 1 every output is bitwise dq_dqn_huber_loss's on
+ * (online_q, target_next_q).  A NULL required pointer, batch or num_actions < 1, tau not finite
+ * or <= 0, alpha not finite or < 0, clip_min not finite or > 0, or a mean_loss_out without a
+ * loss_out is DQ_E_ARG before a launch, with nothing written. */
+int dq_mdqn_loss(const float* online_q, const float* target_next_q, const float* target_cur_q,
+                 const int32_t* actions, const float* rewards, const uint8_t* terminals,
+                 int32_t batch, int32_t num_actions, float cumulative_gamma, float tau,
+                 float alpha, float clip_min, float* grad_q, float* loss_out,
+                 float* mean_loss_out, void* stream);
 
 /* IQN quantile-Huber loss (implicit_quantile_agent.py:190-321).  Row order of
  * the tiled tensors is q*B + b (atari_lib.py:174).  grad (N*B, A) fully written. */

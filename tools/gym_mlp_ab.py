@@ -22,7 +22,8 @@ quantile_cartpole / double_quantile_cartpole / quantile_acrobot (QR-DQN, 200 qua
 dueling_double_dqn_acrobot / dueling_rainbow_cartpole / dueling_quantile_cartpole (the dueling
 heads; their parents are double_dqn_acrobot / double_rainbow_cartpole / quantile_cartpole) and
 noisy_dqn_acrobot / full_rainbow_cartpole / noisy_quantile_cartpole (the noisy layers; their
-parents are dqn_acrobot / dueling_rainbow_cartpole / quantile_cartpole).
+parents are dqn_acrobot / dueling_rainbow_cartpole / quantile_cartpole) and mdqn_cartpole /
+mdqn_acrobot / dueling_mdqn_acrobot (Munchausen-DQN; their parents are dqn_cartpole / dqn_acrobot).
 --profile-arm runs 300 learner steps and 300 agent steps of the HIP arm only, of every config
 named (the run to put under a kernel-trace profiler for the per-launch table)."""
 import argparse
@@ -80,6 +81,10 @@ CONFIGS['full_rainbow_cartpole'] = (
     os.path.join(_AGENTS, 'rainbow', 'configs', 'full_rainbow_cartpole.gin'), 'RainbowAgent')
 CONFIGS['noisy_quantile_cartpole'] = (
     os.path.join(_AGENTS, 'quantile', 'configs', 'noisy_quantile_cartpole.gin'), 'QuantileAgent')
+# Munchausen-DQN (dq_mdqn_loss and the target network's forward on state): name the parent
+# config too for the flag's cost in the same session
+for _n in ('mdqn_cartpole', 'mdqn_acrobot', 'dueling_mdqn_acrobot'):
+  CONFIGS[_n] = (os.path.join(_AGENTS, 'dqn', 'configs', _n + '.gin'), 'DQNAgent')
 DEFAULT_CONFIGS = ['rainbow_cartpole', 'dqn_cartpole']
 
 
